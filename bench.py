@@ -14,7 +14,9 @@ slice and the partial groups are merged (one small all-gather), Q3's joins go th
 qurious_amd/exchange.py over RCCL (--strategy broadcast: all-gather the small build sides; repartition: all-to-all both
 sides by key hash; both are measured at N > 1, `value` uses --strategy).
 
-Rank 0 prints ONE JSON line. Besides the contract's fields it carries
+Rank 0 prints ONE JSON line. A plain run does only what its headline needs: it generates and uploads the tables, warms up,
+times K steps and prints `metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` (wall time of one timed step)
+and the configuration. With --full (off by default) it then measures everything else as well; the line then also carries
   roofline      the step's dominant kernel (Q1's fused filter + aggregate): bytes the kernel actually reads per launch /
                 its mean device time (HIP events on the library's stream) against the 8 TB/s HBM peak; `traffic` = HBM
                 bytes per launch from this round's PMC profile (profiles/r03_pmc_summary.json) when that profile was taken
@@ -28,6 +30,15 @@ Rank 0 prints ONE JSON line. Besides the contract's fields it carries
 
 Other modes: --workload q1_mini | q1_full | q3 | filter run ONE configuration as the step (profiling, parameter sweeps);
 --workload q3 --sf 100 --skew 1.1 --slice R/N generates only rank R's 1/N slice of SF100 (BASELINE configs[4] on one GPU).
+q1_* and q3 likewise print only the headline unless --full is given (then their record, roofline and CPU baseline); the
+filter and partition modes always print their per-case records.
+
+--dump-outputs DIR (metric, q1_* and q3 workloads): after the timed steps, the results of the last step as a caller of the
+plan receives them (execute() -> Arrow batches), one DIR/<query>_<column index>_<column name>.npy per column in float64:
+numbers and decimals by value, dates as days since 1970-01-01, strings as a [rows, longest] matrix of their UTF-8 bytes
+(0-padded), NULL as NaN. The rows are sorted on all columns (the groups of a hash aggregate come in no fixed order) and, should
+all of them together exceed 64 MB, a fixed seeded sample of the sorted rows is written. The synthetic inputs depend only on the
+arguments, so two builds run with the same arguments can be compared array for array.
 """
 import argparse
 import json
@@ -53,6 +64,7 @@ SF10_LINEITEM_ROWS = 59_986_052
 PMC_SUMMARY = next((p for p in (os.path.join(ROOT, "profiles", f"r0{r}_pmc_summary.json") for r in (4, 3)) if os.path.exists(p)),
                    os.path.join(ROOT, "profiles", "r04_pmc_summary.json"))   # this round's PMC passes (tools/pmc_passes.sh); the last round's until they exist
 SETTLE_STEPS = 3   # untimed executions in front of the W warm-up steps: a plan reaches its steady state on its third execution
+DUMP_LIMIT_BYTES = 64 << 20   # --dump-outputs: at most this many bytes of .npy data in all
 
 USE_DIST = False   # set by main(): a torch.distributed process group (RCCL) is up
 
@@ -251,6 +263,72 @@ def median_runs(fn, runs=5):
     return statistics.median(times), times, res
 
 
+# ---------------------------------------------------------------- outputs (--dump-outputs)
+def column_as_float(col):
+    """One result column as float64 (see the module docstring): a 1-D array, or [rows, longest] bytes for strings."""
+    import numpy as np
+    import pyarrow as pa
+    t = col.type
+    if pa.types.is_string(t) or pa.types.is_large_string(t) or pa.types.is_binary(t) or pa.types.is_large_binary(t):
+        vals = [v if v is None or isinstance(v, bytes) else v.encode() for v in col.to_pylist()]
+        out = np.zeros((len(vals), max([len(v) for v in vals if v is not None] + [1])), dtype=np.float64)
+        for i, v in enumerate(vals):
+            if v is None:
+                out[i, :] = np.nan
+            else:
+                out[i, :len(v)] = np.frombuffer(v, dtype=np.uint8)
+        return out
+    if pa.types.is_decimal(t):   # (float(Decimal) rounds to nearest; Arrow's cast to float64 does not always)
+        return np.array([np.nan if v is None else float(v) for v in col.to_pylist()], dtype=np.float64)
+    if pa.types.is_date32(t):
+        col = col.cast(pa.int32())
+    elif pa.types.is_temporal(t):
+        col = col.cast(pa.int64())
+    elif pa.types.is_boolean(t):
+        col = col.cast(pa.int8())
+    return np.asarray(col.cast(pa.float64()).to_numpy(zero_copy_only=False), dtype=np.float64)
+
+
+def dump_outputs(out_dir, results):
+    """results: {query: (plan, device table of its last timed execution)} -> DIR/<query>_<k>_<column>.npy (module docstring)."""
+    import re
+    import numpy as np
+    import pyarrow as pa
+    os.makedirs(out_dir, exist_ok=True)
+    tables = {}
+    for name, (plan, dev) in results.items():
+        schema = plan.schema()
+        batches = [qplan._with_schema(b, schema) for b in dev.to_batches()]   # what plan.execute() hands its caller
+        cols = []
+        for k, f in enumerate(schema):
+            arr = pa.concat_arrays([b.column(k) for b in batches]) if batches else pa.array([], type=f.type)
+            cols.append((f.name, column_as_float(arr)))
+        keys = []
+        for _, c in cols:
+            keys.extend([c] if c.ndim == 1 else [c[:, j] for j in range(c.shape[1])])
+        order = np.lexsort(keys[::-1]) if keys else np.zeros(0, dtype=np.int64)
+        tables[name] = [(n, c[order]) for n, c in cols]
+    # the byte budget is shared out smallest output first: one that fits its even share is written whole, a bigger one as a
+    # seeded sample of its sorted rows
+    budget, written = DUMP_LIMIT_BYTES - (1 << 20), 0   # (1 MB left for the .npy headers)
+    by_size = sorted(tables, key=lambda n: sum(c.nbytes for _, c in tables[n]))
+    for left, name in zip(range(len(by_size), 0, -1), by_size):
+        cols = tables[name]
+        rows = len(cols[0][1]) if cols else 0
+        nbytes = sum(c.nbytes for _, c in cols)
+        if nbytes > budget // left:
+            keep = (budget // left) // max(1, nbytes // max(1, rows))
+            pick = np.sort(np.random.default_rng(20241016).choice(rows, keep, replace=False))
+            cols = [(n, c[pick]) for n, c in cols]
+            log(f"dump: {name}: a seeded sample of {keep} of its {rows} rows")
+        for k, (n, c) in enumerate(cols):
+            np.save(os.path.join(out_dir, f"{name}_{k:02d}_{re.sub(r'[^A-Za-z0-9_]+', '_', n)}.npy"), c)
+            budget -= c.nbytes
+            written += c.nbytes
+        log(f"dump: {name}: {len(cols[0][1]) if cols else 0} rows x {len(cols)} columns")
+    log(f"dump: {written} bytes of float64 under {out_dir}")
+
+
 # ---------------------------------------------------------------- CPU baselines (rank 0, N = 1 only)
 def cpu_scan_aggregate(workload, table, batch_rows, sample_rows):
     """The oracle's qo_scan_filter_aggregate (per-batch literal broadcast + cast + compare, compaction of all 7 columns,
@@ -301,13 +379,15 @@ class Q1:
         dev = self.table.device_table()
         self.t_upload = time.time() - t0
         self.resident = sum(dev.column_bytes(c) for c in range(dev.num_columns))
-        # the same upload once more into a second table (dropped at once): the first one pays ~40 ms of hipMalloc page mapping
-        # for the pool's first 4.7 GB on top of the transfer, this one shows the transfer (DESIGN §6 "Upload")
-        t0 = time.time()
-        again = q.DeviceTable.from_batches(ctx, self.table.schema(), self.table.data)
-        ctx.synchronize()
-        self.t_upload_warm = time.time() - t0
-        del again
+        self.t_upload_warm = None
+        if args.full:
+            # the same upload once more into a second table (dropped at once): the first one pays ~40 ms of hipMalloc page mapping
+            # for the pool's first 4.7 GB on top of the transfer, this one shows the transfer (DESIGN §6 "Upload")
+            t0 = time.time()
+            again = q.DeviceTable.from_batches(ctx, self.table.schema(), self.table.data)
+            ctx.synchronize()
+            self.t_upload_warm = time.time() - t0
+            del again
         # N > 1: every rank aggregates its slice into partial groups (AVG planned as SUM and COUNT) that are merged after one
         # small all-gather; N = 1: the query as the reference's planner builds it
         self.plan = queries.q1_partial(self.table) if USE_DIST and workload == "q1_full" else getattr(queries, workload)(self.table)
@@ -315,23 +395,35 @@ class Q1:
         log(f"{workload}: {self.rows} rows generated in {self.t_gen:.1f}s, uploaded in {self.t_upload:.1f}s")
 
     def step(self):
-        out = self.plan.execute_device()
+        out = self.out = self.plan.execute_device()
         if USE_DIST:
             self.merged = merge_partial_groups(self.plan, out)
         return out
 
-    def record(self, args, clock, with_cpu):
+    def setup_s(self):
+        s = {"generate": self.t_gen, "upload_h2d": self.t_upload, "h2d_GBps": self.resident / max(self.t_upload, 1e-9) / 1e9}
+        if self.t_upload_warm is not None:
+            s["h2d_GBps_warm_allocator"] = self.resident / max(self.t_upload_warm, 1e-9) / 1e9
+        return s
+
+    def record(self, args, clock, with_cpu, after_timed=None):
         elapsed = clock.run(self.step, args.steps, args.warmup)
+        if after_timed:
+            after_timed()
+        cfg = "configs[1]" if self.workload == "q1_mini" else "configs[2]"
+        what = ("filter + GROUP BY l_returnflag, SUM(l_quantity)" if self.workload == "q1_mini" else
+                "TPC-H Q1: 2 keys, 4 SUM + 3 AVG + COUNT (q1.slt:5-12)")
+        workload = (f"{cfg} {self.workload}: {what} over {self.rows_total} synthetic lineitem rows "
+                    f"({args.batch_rows}-row Arrow batches, HBM-resident, {self.world} rank(s))")
+        if not args.full:
+            return {"workload": workload, "value": self.rows_total * args.steps / elapsed, "unit": "rows/s", "steps": args.steps,
+                    "ms_per_step": elapsed / args.steps * 1e3, "rows": self.rows_total, "groups": self.out.num_rows}, elapsed
         ops = operator_stats(self.step)
         st = ops[-1]
         bpr = min(SURVEY_BYTES_PER_ROW[self.workload], st.get("bytes_per_row_read") or SURVEY_BYTES_PER_ROW[self.workload])
         kbytes = self.rows * bpr
         traffic, src = pmc_traffic(self.workload, st["main_kernel_name"], self.rows, bpr)
-        cfg = "configs[1]" if self.workload == "q1_mini" else "configs[2]"
-        what = ("filter + GROUP BY l_returnflag, SUM(l_quantity)" if self.workload == "q1_mini" else
-                "TPC-H Q1: 2 keys, 4 SUM + 3 AVG + COUNT (q1.slt:5-12)")
-        rec = {"workload": f"{cfg} {self.workload}: {what} over {self.rows_total} synthetic lineitem rows "
-                           f"({args.batch_rows}-row Arrow batches, HBM-resident, {self.world} rank(s))",
+        rec = {"workload": workload,
                "value": self.rows_total * args.steps / elapsed, "unit": "rows/s", "steps": args.steps, "ms_per_step": elapsed / args.steps * 1e3,
                "rows": self.rows_total, "groups": st["groups"], "resident_bytes_per_gpu": self.resident,
                "roofline": roofline(st["main_kernel_name"], st["main_kernel_ms"], kbytes, traffic, src,
@@ -435,15 +527,29 @@ class Q3:
             vals = t.tolist()
         return vals
 
-    def record(self, args, clock, torch, dist, with_cpu, strategy=None, extras=True):
+    def workload(self, strategy):
+        cfg = "configs[4]" if self.skew > 0 else "configs[3]"
+        par = ("one GPU" if not USE_DIST else f"broadcast build sides, local probes, merged partial groups x{self.world}" if strategy == "broadcast"
+               else f"both join sides repartitioned by key hash (all-to-all) x{self.world}")
+        return (f"{cfg} q3: TPC-H Q3 (q3.slt:1-24) SF{self.sf} customer|><|orders|><|lineitem + GROUP BY, HBM-resident"
+                + (f", join keys re-drawn from Zipf(s={self.skew})" if self.skew > 0 else "")
+                + (f", slice {self.slice_of[0]}/{self.slice_of[1]} of every table on one GPU" if self.slice_of else "") + f"; {par}")
+
+    def record(self, args, clock, torch, dist, with_cpu, strategy=None, extras=True, after_timed=None):
         strategy = strategy or self.strategy
         ex = self.exchange
         if USE_DIST:
             ex.exchange_stats(reset=True)
         elapsed = clock.run(lambda: self.step(strategy), args.steps, args.warmup)
+        if after_timed:
+            after_timed()
         lib_waits = clock.timed_waits            # over the K timed steps (the settling executions wait more: sizes not learnt yet)
         xg = ex.exchange_stats(reset=True) if USE_DIST else None
         tot = self.totals(torch, dist)
+        if not args.full:
+            return {"workload": self.workload(strategy), "value": tot[2] * args.steps / elapsed, "unit": "lineitem rows/s", "steps": args.steps,
+                    "ms_per_step": elapsed / args.steps * 1e3, "rows": {"customer": tot[0], "orders": tot[1], "lineitem": tot[2]},
+                    "groups": tot[3], "strategy": strategy if USE_DIST else None}, elapsed
         ops = operator_stats(lambda: self.step(strategy), passes=3)
         joins = [o for o in ops if o["operator"] == "hash_join"]
         aggs = [o for o in ops if o["operator"] == "aggregate"]
@@ -477,12 +583,7 @@ class Q3:
                                 operator="aggregate", groups=a["groups"]))
         dominant = max(kernels, key=lambda k: k["kernel_ms"]) if kernels else None
         survey = tot[0] * Q3_SURVEY_BYTES["customer"] + tot[1] * Q3_SURVEY_BYTES["orders"] + tot[2] * Q3_SURVEY_BYTES["lineitem"]
-        cfg = "configs[4]" if self.skew > 0 else "configs[3]"
-        par = ("one GPU" if not USE_DIST else f"broadcast build sides, local probes, merged partial groups x{self.world}" if strategy == "broadcast"
-               else f"both join sides repartitioned by key hash (all-to-all) x{self.world}")
-        rec = {"workload": f"{cfg} q3: TPC-H Q3 (q3.slt:1-24) SF{self.sf} customer|><|orders|><|lineitem + GROUP BY, HBM-resident"
-                           + (f", join keys re-drawn from Zipf(s={self.skew})" if self.skew > 0 else "")
-                           + (f", slice {self.slice_of[0]}/{self.slice_of[1]} of every table on one GPU" if self.slice_of else "") + f"; {par}",
+        rec = {"workload": self.workload(strategy),
                "value": tot[2] * args.steps / elapsed, "unit": "lineitem rows/s", "steps": args.steps, "ms_per_step": elapsed / args.steps * 1e3,
                "rows": {"customer": tot[0], "orders": tot[1], "lineitem": tot[2]}, "groups": tot[3], "strategy": strategy if USE_DIST else None,
                "roofline": dominant, "kernels": kernels,
@@ -671,9 +772,18 @@ def main():
     ap.add_argument("--slice", default="", help="Q3 on ONE GPU over rank R's 1/N slice of every table, as R/N (configs[4]: --sf 100 --skew 1.1 --slice 0/8)")
     ap.add_argument("--cpu-sample-rows", type=int, default=16 << 20, help="rows of a q1_* workload timed through the CPU oracle (per run)")
     ap.add_argument("--cpu-q3-sf", type=float, default=2.0, help="scale factor of the Q3 sample timed through the CPU oracle")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="N = 1: skip the q1_mini and Filter records")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-extra", action="store_true", help="--full, N = 1: skip the q1_mini and Filter records")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, measure everything else too: per-configuration records, rooflines, CPU baselines, cold and "
+                         "export timings, other join layouts and strategies, the q1_mini / Filter / partition / C++ host records")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write the results of the last timed step to DIR/<query>_<column>.npy (float64; metric, q1_* and q3 workloads)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and args.workload in ("filter", "partition"):
+        ap.error("--dump-outputs is available for the metric, q1_mini, q1_full and q3 workloads")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -699,13 +809,13 @@ def main():
         except Exception:
             rccl = None
     clock = Clock(ctx, torch, dist)
-    with_cpu = not args.no_cpu_baseline and world == 1 and not USE_DIST
+    with_cpu = args.full and not args.no_cpu_baseline and world == 1 and not USE_DIST
     log("torch imported")
     line = {"metric": METRIC, "unit": "rows/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "higher_is_better": True,
             "vs_baseline": None, "dtype": "i128", "data": "synthetic", "device": ctx.device_name(),
             "state": f"warm: the timed steps repeat cached plans over resident tables ({SETTLE_STEPS} untimed settling executions + W warm-up "
-                     "steps first: learnt join sizes, one host wait per query, remembered group counts); records.*.first_execution_ms = a new "
-                     "plan with that knowledge forgotten (code cache warm), records.*.execute_with_export_ms = through execute() to host Arrow batches"}
+                     "steps first: learnt join sizes, one host wait per query, remembered group counts); with --full, records.*.first_execution_ms "
+                     "= a new plan with that knowledge forgotten (code cache warm), records.*.execute_with_export_ms = through execute() to host Arrow batches"}
     if USE_DIST:
         line["distributed"] = {"world_size": dist.get_world_size(), "backend": "nccl (RCCL)", "rccl_version": rccl}
 
@@ -715,16 +825,21 @@ def main():
         if USE_DIST:
             dist.destroy_process_group()
 
+    def dump(results):
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, results)
+
     # ---- single-configuration modes (profiling / sweeps): the chosen configuration is the step
     if args.workload in ("q1_mini", "q1_full"):
         rows = args.rows or (100_000_000 if args.workload == "q1_mini" else SF10_LINEITEM_ROWS)
         w = Q1(args, ctx, args.workload, rows, rank, world)
-        rec, elapsed = w.record(args, clock, with_cpu)
-        line.update(value=rec["value"], ms_per_step=rec["ms_per_step"], scaling="strong", roofline=rec["roofline"], cpu_baseline=rec["cpu_baseline"],
-                    config={"workload": rec["workload"], "rows": rows, "batch_rows": args.batch_rows, "groups": rec["groups"],
+        rec, elapsed = w.record(args, clock, with_cpu, after_timed=lambda: dump({args.workload: (w.plan, w.out)}))
+        line.update(value=rec["value"], ms_per_step=rec["ms_per_step"], scaling="strong")
+        if args.full:
+            line.update(roofline=rec["roofline"], cpu_baseline=rec["cpu_baseline"])
+        line.update(config={"workload": rec["workload"], "rows": rows, "batch_rows": args.batch_rows, "groups": rec["groups"],
                             "parallelism": f"row-range slices x{world}, partial groups merged"},
-                    setup_s={"generate": w.t_gen, "upload_h2d": w.t_upload, "h2d_GBps": w.resident / max(w.t_upload, 1e-9) / 1e9,
-                             "h2d_GBps_warm_allocator": w.resident / max(w.t_upload_warm, 1e-9) / 1e9})
+                    setup_s=w.setup_s())
         return finish()
     if args.workload == "filter":
         rows = args.rows or SF10_LINEITEM_ROWS
@@ -743,8 +858,12 @@ def main():
     if args.workload == "q3":
         slice_of = tuple(int(x) for x in args.slice.split("/")) if args.slice else None
         w = Q3(args, ctx, rank, world, args.strategy, slice_of)
-        rec, elapsed = w.record(args, clock, torch, dist, with_cpu)
-        line.update(value=rec["value"], ms_per_step=rec["ms_per_step"], scaling="strong", roofline=rec["roofline"], cpu_baseline=rec["cpu_baseline"],
+        rec, elapsed = w.record(args, clock, torch, dist, with_cpu, after_timed=lambda: dump({"q3": (w.plan(args.strategy), w.out)}))
+        line.update(value=rec["value"], ms_per_step=rec["ms_per_step"], scaling="strong")
+        if not args.full:
+            line["config"] = {"workload": rec["workload"], "rows": rec["rows"], "groups": rec["groups"]}
+            return finish()
+        line.update(roofline=rec["roofline"], cpu_baseline=rec["cpu_baseline"],
                     config={"workload": rec["workload"], "rows": rec["rows"], "groups": rec["groups"]}, records={"q3": rec})
         if args.skew > 0 or os.environ.get("QHIP_AGG_STATS"):
             line["aggregate_table"] = w.table_stats()
@@ -762,9 +881,23 @@ def main():
         q3.step()
 
     elapsed = clock.run(step, args.steps, args.warmup)
+    dump({"q1": (q1.plan, q1.out), "q3": (q3.plan(args.strategy), q3.out)})
     tot = q3.totals(torch, dist)
     rows_step = SF10_LINEITEM_ROWS + tot[2]
     log(f"timed {args.steps} steps in {elapsed:.3f}s")
+    config = {"workload": "configs[2] TPC-H Q1 (aggregate list, q1.slt:5-12) over SF10's 59986052 lineitem rows + configs[3] TPC-H Q3 "
+                          "(q3.slt:1-24) at SF10, one pass of each per step; value = lineitem rows scanned by both / wall time; "
+                          "synthetic Arrow tables (SURVEY §8d recipes), HBM-resident",
+              "rows_per_step": {"q1_lineitem": SF10_LINEITEM_ROWS, "q3_customer": tot[0], "q3_orders": tot[1], "q3_lineitem": tot[2]},
+              "batch_rows": args.batch_rows, "q1_groups": q1.out.num_rows, "q3_groups": tot[3],
+              "resident_bytes_per_gpu": q1.resident,
+              "parallelism": "one GPU" if not USE_DIST else f"every table sliced over {world} ranks; Q1 partial groups merged by all-gather, "
+                                                               f"Q3 joins: {args.strategy}"}
+    setup_s = {"q1_generate": q1.t_gen, "q1_upload_h2d": q1.t_upload, "h2d_GBps": q1.resident / max(q1.t_upload, 1e-9) / 1e9}
+    if not args.full:
+        line.update(value=rows_step * args.steps / elapsed, ms_per_step=elapsed / args.steps * 1e3, scaling="strong", config=config,
+                    setup_s=dict(setup_s, note="h2d_GBps = the process's FIRST upload (includes the allocator's first hipMalloc of the table's bytes)"))
+        return finish()
     records = {}
     records["q1_sf10"], _ = q1.record(args, clock, with_cpu)
     records["q3_sf10"], _ = q3.record(args, clock, torch, dist, with_cpu)
@@ -817,22 +950,14 @@ def main():
                "sample": "the step's two queries at the rates of their bounded samples (records.q1_sf10.cpu_baseline, records.q3_sf10.cpu_baseline: "
                          f"oracle/qoracle.c, 1 of {os.cpu_count()} host cores, 1 warm-up + median of 5 each)",
                "parts": {"q1_sf10_rows_per_s": c1["value"], "q3_sf10_lineitem_rows_per_s": c3["value"]}}
-    line.update(value=rows_step * args.steps / elapsed, ms_per_step=elapsed / args.steps * 1e3, scaling="strong",
-                config={"workload": "configs[2] TPC-H Q1 (aggregate list, q1.slt:5-12) over SF10's 59986052 lineitem rows + configs[3] TPC-H Q3 "
-                                    "(q3.slt:1-24) at SF10, one pass of each per step; value = lineitem rows scanned by both / wall time; "
-                                    "synthetic Arrow tables (SURVEY §8d recipes), HBM-resident",
-                        "rows_per_step": {"q1_lineitem": SF10_LINEITEM_ROWS, "q3_customer": tot[0], "q3_orders": tot[1], "q3_lineitem": tot[2]},
-                        "batch_rows": args.batch_rows, "q1_groups": records["q1_sf10"]["groups"], "q3_groups": tot[3],
-                        "resident_bytes_per_gpu": q1.resident,
-                        "parallelism": "one GPU" if not USE_DIST else f"every table sliced over {world} ranks; Q1 partial groups merged by all-gather, "
-                                                                         f"Q3 joins: {args.strategy}"},
+    config["q1_groups"] = records["q1_sf10"]["groups"]
+    line.update(value=rows_step * args.steps / elapsed, ms_per_step=elapsed / args.steps * 1e3, scaling="strong", config=config,
                 roofline=records["q1_sf10"]["roofline"], cpu_baseline=cpu, records=records,
                 execute_with_export_ms=(None if USE_DIST else records["q1_sf10"].get("execute_with_export_ms", 0) + records["q3_sf10"].get("execute_with_export_ms", 0)),
                 cold_first_step_ms=(None if USE_DIST else records["q1_sf10"]["cold_table"]["cold_first_query_ms"] + records["q3_sf10"]["cold_table"]["cold_first_query_ms"]),
-                setup_s={"q1_generate": q1.t_gen, "q1_upload_h2d": q1.t_upload, "h2d_GBps": q1.resident / max(q1.t_upload, 1e-9) / 1e9,
-                         "h2d_GBps_warm_allocator": q1.resident / max(q1.t_upload_warm, 1e-9) / 1e9,
-                         "note": "h2d_GBps = the process's FIRST upload (includes the allocator's first hipMalloc of the table's bytes); "
-                                 "_warm_allocator = the same upload repeated into pooled memory = the transfer itself"})
+                setup_s=dict(setup_s, h2d_GBps_warm_allocator=q1.resident / max(q1.t_upload_warm, 1e-9) / 1e9,
+                             note="h2d_GBps = the process's FIRST upload (includes the allocator's first hipMalloc of the table's bytes); "
+                                  "_warm_allocator = the same upload repeated into pooled memory = the transfer itself"))
     if "exchange" in records["q3_sf10"]:
         line["exchange"] = records["q3_sf10"]["exchange"]
     if world == 1 and not USE_DIST and not args.no_extra:

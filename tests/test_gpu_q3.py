@@ -206,11 +206,11 @@ def test_multi_rank_code_path_rehearsal_on_one_gpu():
     env.update(QHIP_BENCH_FORCE_DIST="1", QHIP_EXCHANGE_FORCE="1", MASTER_PORT="29549", RANK="0", WORLD_SIZE="1", LOCAL_RANK="0",
                QHIP_BENCH_ZIPF_SF="0.2")   # (the configs[4] record of the N > 1 line at a size that fits a test)
     # (1) exactly the command the driver's scaling run issues per rank (default workload: the metric's step = Q1 at SF10 +
-    # Q3 at SF10), with the multi-rank branch forced on: Q1 partial groups merged through an all-gather, Q3 through both
-    # exchange strategies; (2) single-configuration modes at small sizes
+    # Q3 at SF10), with the multi-rank branch forced on and --full's records: Q1 partial groups merged through an all-gather,
+    # Q3 through both exchange strategies; (2) single-configuration modes at small sizes
     for extra in ([], ["--workload", "q1_full", "--rows", "3000000"], ["--workload", "q3", "--sf", "0.2"],
                   ["--workload", "q3", "--sf", "0.2", "--strategy", "repartition"]):
-        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1"] + extra,
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--full"] + extra,
                            env=env, capture_output=True, text=True, timeout=900)
         assert r.returncode == 0, r.stderr[-4000:]
         line = json.loads(r.stdout.strip().splitlines()[-1])

@@ -76,7 +76,7 @@ def main():
                                 "traffic_over_bytes_read": (h["hbm_bytes_per_launch"] / (w[1] * w[2])) if w[2] else None})
         summary[tag] = {"collected": label, "correction": "gfx950: FETCH_SIZE x 2 (128-byte requests tallied at 64 bytes), WRITE_SIZE exact; "
                                                            "separate --pmc passes (MI355X_MICROARCH.md)",
-                        "command": f"tools/pmc_passes.sh <dir> {tag} --workload {tag} ... (rocprofv3 --pmc <group> --kernel-trace -- python3 bench.py)",
+                        "command": f"tools/pmc_passes.sh <dir> {tag} --workload {tag} ... (rocprofv3 --pmc <group> --kernel-trace -- python3 bench.py --full)",
                         "kernels": kernels}
     if "partition" in summary:
         whole = summary.pop("partition")

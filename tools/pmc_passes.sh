@@ -23,9 +23,9 @@ GROUPS_=(
 i=0
 for g in "${GROUPS_[@]}"; do
   if [ -n "$PMC_ONLY" ] && ! echo " $PMC_ONLY " | grep -q " $i "; then i=$((i+1)); continue; fi
-  timeout -k 10 300 rocprofv3 --pmc $g --kernel-trace --output-format csv -d $OUT/pmc_${TAG}_$i -o $TAG -- python3 bench.py "$@" > $OUT/pmc_${TAG}_$i.json 2> $OUT/pmc_${TAG}_$i.err
+  timeout -k 10 300 rocprofv3 --pmc $g --kernel-trace --output-format csv -d $OUT/pmc_${TAG}_$i -o $TAG -- python3 bench.py --full "$@" > $OUT/pmc_${TAG}_$i.json 2> $OUT/pmc_${TAG}_$i.err
   echo "pmc pass $i ($g) exit $?"
   i=$((i+1))
 done
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_$TAG -o $TAG -- python3 bench.py "$@" > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_$TAG -o $TAG -- python3 bench.py --full "$@" > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err
 echo "trace exit $?"

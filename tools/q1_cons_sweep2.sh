@@ -4,7 +4,7 @@ OUT=$1
 run() {
   WL=$1; shift
   echo "== $WL $*" >> $OUT
-  env "$@" timeout -k 10 200 python bench.py --workload $WL --steps 10 --no-cpu-baseline 2>/dev/null | python -c "
+  env "$@" timeout -k 10 200 python bench.py --full --workload $WL --steps 10 --no-cpu-baseline 2>/dev/null | python -c "
 import sys,json
 l=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=l['roofline']
 print('   kernel', r['kernel'], 'kernel_ms %.4f' % r['kernel_ms'], 'frac %.3f' % r['frac'], 'step ms %.4f' % l['ms_per_step'])" >> $OUT 2>&1

@@ -5,7 +5,7 @@ set -o pipefail
 export TMPDIR=/tmp
 OUT=$1; shift
 mkdir -p $OUT
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o q3 -- python3 bench.py --workload q3 --sf 10 --steps 10 --warmup 2 --no-cpu-baseline "$@" > $OUT/bench.json 2> $OUT/bench.err || { tail -5 $OUT/bench.err; exit 1; }
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o q3 -- python3 bench.py --full --workload q3 --sf 10 --steps 10 --warmup 2 --no-cpu-baseline "$@" > $OUT/bench.json 2> $OUT/bench.err || { tail -5 $OUT/bench.err; exit 1; }
 python3 - $OUT <<'PY'
 import csv, sys, glob, json
 out = sys.argv[1]
