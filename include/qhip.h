@@ -349,6 +349,13 @@ int qhip_partition_filtered_by_range(qhip_ctx* ctx, const qhip_table* input,
 /* [min, max] of an integer-like column's values (NULL slots included as stored), computed once per base column and cached; a
  * column that is a deferred gather answers with its SOURCE's range (a superset). QHIP_UNSUPPORTED for other column types. */
 int qhip_table_column_range(qhip_ctx* ctx, const qhip_table* t, int64_t col, int64_t* out_min, int64_t* out_max);
+/* *out = 1 when the column's values are known strictly ascending (no NULLs): computed with the range; a deferred gather or a
+ * filtered column counts only through an index that keeps the order (the probe side of an Inner join with unique build keys,
+ * a Filter's compaction). What decides the sorted form of a dense join build (QHIP_JOIN_DENSE_SORTED). */
+int qhip_table_column_ascending(qhip_ctx* ctx, const qhip_table* t, int64_t col, int32_t* out);
+/* Sorted dense join builds launched on this context, and how many of them found their keys out of order (or too wide a gap)
+ * and ran again with the atomic build. */
+int qhip_ctx_sorted_build_counts(qhip_ctx* ctx, int64_t* launched, int64_t* fallbacks);
 /* Concatenate tables with identical schemas (batches appended in order). */
 int qhip_table_concat(qhip_ctx* ctx, const qhip_table* const* tables, int32_t n, qhip_table** out);
 

@@ -1051,6 +1051,7 @@ void plan_keys(const ExprSet& es, const std::vector<InputCol>& input, const int3
     g.emit(predicate_root, code);
   }
   emit_key_words(g, es, out.keys, false, "k", code, &all);
+  const std::string key_all = all;   // (the keys alone, before a fused scan filter joins in)
   // (the exchange's partition kernel tells "rejected by the filter" (the row is dropped) from "NULL key" (the row travels, hashed
   // as all-zero key words): bit 1 / bit 0 of what keys() returns)
   if (kernel == KEYS_KERNEL_PARTITION)
@@ -1074,7 +1075,12 @@ void plan_keys(const ExprSet& es, const std::vector<InputCol>& input, const int3
   } else {
     s << "  __device__ static __forceinline__ bool keys(const KArgs& a, const i64 i, u64* k, u32& err) {\n" << code;
   }
-  s << "    return " << all << ";\n  }\n};\n";
+  s << "    return " << all << ";\n  }\n";
+  // the sorted dense build tells a NULL key (bit 0 clear) from a row its fused scan filter rejects (bit 1 clear)
+  if (kernel == KEYS_KERNEL_DENSE_BUILD)
+    s << "  __device__ static __forceinline__ u32 key_state(const KArgs& a, const i64 i, u64* k, u32& err) {\n" << code
+      << "    return ((" << key_all << ") ? 1u : 0u) | ((" << all << ") ? 2u : 0u);\n  }\n";
+  s << "};\n";
   if (kernel == KEYS_KERNEL_PROBE) {
     const int waves = env_int("QHIP_PROBE_WAVES", out.probe_r >= 4 ? 5 : out.probe_r == 3 ? 6 : 8);
     // two entry points: the region layout of the LDS-staged build (the rule) and the one-table legacy layout. Five waves per
@@ -1098,6 +1104,8 @@ void plan_keys(const ExprSet& es, const std::vector<InputCol>& input, const int3
     s << "extern \"C\" __global__ __launch_bounds__(QH_BLOCK) void qk_part_ids_wide(KArgs a, PartIdsLaunch L) { qh_part_ids_body<P, " << (dev_rows ? "true" : "false") << ", true>(a, L); }\n";
   } else if (kernel == KEYS_KERNEL_DENSE_BUILD) {
     s << "extern \"C\" __global__ __launch_bounds__(QH_BLOCK) void qk_join_dense_build(KArgs a, DenseBuildLaunch L) { qh_join_dense_build_body<P" << (dev_rows ? ", true" : "") << ">(a, L); }\n";
+    // ... and the build over strictly ascending keys (no atomics, no cleared bitmap), launched when the key is known to ascend
+    s << "extern \"C\" __global__ __launch_bounds__(QH_BLOCK) void qk_join_dense_build_sorted(KArgs a, DenseSortedLaunch L) { qh_join_dense_build_sorted_body<P" << (dev_rows ? ", true" : "") << ">(a, L); }\n";
   } else if (kernel == KEYS_KERNEL_SCATTER)
     s << "extern \"C\" __global__ __launch_bounds__(QH_SCATTER_BLOCK) void qk_join_scatter(KArgs a, ScatterLaunch L) { qh_join_scatter_body<P" << (dev_rows ? ", true" : "") << ">(a, L); }\n";
   else

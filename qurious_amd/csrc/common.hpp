@@ -98,6 +98,7 @@ inline void copy_sync(hipStream_t s, void* dst, const void* src, size_t n, hipMe
 
 struct ColRange {
   bool known = false; int64_t min = 0, max = 0;
+  bool ascending = false;   // (found with min / max) every value below its successor, no NULLs: key_ascending reads it
   // (round 4) ... and, for readers that reach the column through a deferred gather's COPY of it (DeferredGather::src — an
   // aggregate over a join output reads lineitem's prices through the join's index vector and never sees the table's own column
   // object): the magnitude bound and the 4- / 8-byte narrow copy of a Decimal128 column, made at the second such read, valid for
@@ -145,6 +146,9 @@ struct DevColumn {
   // (range_inherited: a superset's bounds hold for the subset; the subset never writes its own, narrower, bounds into it).
   mutable std::shared_ptr<struct ColRange> range = std::make_shared<struct ColRange>();
   mutable bool range_inherited = false;
+  // ... and a range_inherited column whose values are those of the range's column in their order, some left out (a Filter's
+  // compaction, a gather through an ascending index vector): the range's `ascending` holds for it too (key_ascending)
+  mutable bool range_order = false;
   // A join / filter output column may be DEFERRED: (source column, row index vector), gathered only when somebody reads
   // it (an expression that references it, an export, an exchange). The reference gathers every column of every join
   // output (utils/batch.rs:18-61) although most are never looked at downstream (Q3: c_mktsegment, o_custkey, ...).
@@ -170,6 +174,7 @@ struct DeferredGather {
   std::shared_ptr<DevBuf> idx;    // u32 row numbers into src; kNullIdx -> NULL when idx_may_be_null
   uint64_t m = 0;
   bool idx_may_be_null = false;
+  bool idx_ascends = false;       // idx is strictly ascending (an Inner join's probe side with unique build keys, a selection)
   bool done = false;
   DevColumn result;
 };
@@ -253,6 +258,8 @@ struct Ctx {
   DevBuf zero_ring;
   size_t zero_next = 0;
   std::unordered_set<uint64_t> join_dup_builds;   // build sides (key policy x row count) seen with duplicate keys: no speculation
+  std::unordered_set<uint64_t> join_unsorted_builds;   // ... seen out of order by the sorted dense build: the atomic build
+  int64_t sorted_builds = 0, sorted_build_fallbacks = 0;   // sorted dense builds launched / found out of order (qhip_ctx_sorted_build_counts)
   // Deferred sizing. A hash join remembers how many pairs it produced (keyed by its expressions, type and probe rows, NOT
   // by the data). The next time the same join runs under a consumer that can read a device-side row count
   // (allow_deferred_sizes > 0: HashAggregate's input, a hash join's build side) it does not wait for its pair total: the

@@ -66,6 +66,14 @@ void verify_pending_sizes(Ctx* ctx) {
     const uint32_t* build = p.slot;                    // [build status | probe status | pair total]
     const uint64_t total = p.slot[2 * QS_WORDS];
     if (p.total_out) *p.total_out = total;
+    if (build[QS_MAXCOUNT] & QS_ORDER_BROKEN) {        // the sorted dense build's keys were out of order: the atomic build next time
+      if (ctx->join_unsorted_builds.size() > 4096) ctx->join_unsorted_builds.clear();
+      ctx->join_unsorted_builds.insert(p.dup_hint);
+      ++ctx->sorted_build_fallbacks;
+      ctx->join_size_hints.erase(p.key);
+      why = "build keys out of order";
+      continue;
+    }
     if (build[QS_MAXCOUNT] > 1) {                      // duplicate build keys after all: remember, run again the careful way
       if (ctx->join_dup_builds.size() > 4096) ctx->join_dup_builds.clear();
       ctx->join_dup_builds.insert(p.dup_hint);
@@ -407,6 +415,7 @@ int qhip_ctx_forget_plans(qhip_ctx* ctx) {
     ctx->plan_cache.clear();
     ctx->join_size_hints.clear();
     ctx->join_dup_builds.clear();
+    ctx->join_unsorted_builds.clear();
     ctx->agg_group_hints.clear();
     ctx->agg_slot_words.clear();
     ctx->pending_sizes.clear();

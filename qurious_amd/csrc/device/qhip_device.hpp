@@ -1797,6 +1797,8 @@ struct ProbeLaunch {
   // [dense_min, dense_min + dense_n) as 32-bit words, `table` = u32 row_of[key - dense_min] (defined only where the bit is set)
   u64 dense_min;
   u32 dense_n, dense_words;          // keys in the range (<= 2^30); 32-bit words of the bitmap
+  const u32* dense_rank;             // rank form of the sorted dense build (row_of unused, qh_dense_build_row), else null
+  u32 dense_last;                    // the build side's last row (qh_dense_build_row clamps to it)
 };
 
 // The build's hash filter is a blocked Bloom filter: FOUR bits per key inside ONE 64-bit word (two in each half), sized at
@@ -2080,6 +2082,118 @@ __device__ __forceinline__ void qh_join_dense_build_body(const KArgs& a, const D
     atomicMax(&L.status[QS_MAXCOUNT], 2u);
 }
 
+// ------------------------------------------------------------------ dense build over STRICTLY ASCENDING build keys
+// A build side whose key column is known strictly ascending (ColRange::ascending, read through an ascending index vector:
+// relops.cpp key_ascending) — Q3's both joins: c_custkey is a base column in key order, join 2's o_orderkey arrives through
+// join 1's probe-side index vector — needs no atomics and no cleared bitmap. A workgroup owns QH_SORTED_ROWS consecutive
+// build rows [r0, r1) and with them every bitmap word w whose first value 32 w has its lower bound (first row with
+// key - kmin >= 32 w) in [r0, r1); the last workgroup with rows also owns the words behind the last key. Word w is then
+// stored exactly once, with a plain store, by the owner of its first key (the words of a gap by the row range behind it),
+// which looks ahead at most 32 keys into the next range. Two forms (the host picks, join.cpp):
+//  * rank form (every build row inserted: no fused scan filter, no NULL keys): rank[w] = the word's lower bound, so that
+//    the build row of a set bit is rank[w] + the set bits below it (qh_dense_build_row) — no row_of[] at all: 8 bytes per
+//    32 key values written as streams instead of 4 scattered bytes per key value;
+//  * row_of form (fused scan filter): bits of the rows that pass the filter, row_of[key - kmin] = row for every row (the keys
+//    ascend, so those stores are in order; row_of is read only where a bit is set).
+// The order is verified here, within each range and across its end (the next range's first key is in the window): equal
+// neighbours raise the duplicate flag (status[QS_MAXCOUNT] = 2), any other descent — or a NULL key, or a gap of more than
+// QH_SORTED_MAX_WORDS words that one workgroup would have to write alone — QS_ORDER_BROKEN; the host then runs the join
+// again with qh_join_dense_build_body. Whatever the data, every store stays inside bits / rank /
+// row_of and every rank is <= the row count (the readers clamp it), so a wrong guess is memory-safe until the host sees it.
+struct DenseSortedLaunch {
+  u32* bits;        // [words]: every word stored here exactly once — no memset beforehand
+  u32* rank;        // rank form: [words], else null
+  u32* row_of;      // row_of form: row_of[key - kmin] = build row, else null
+  u32* status;
+  u64 kmin;
+  u32 n;            // keys in the range
+  u32 words;        // 32-bit words of the bitmap: (n + 31) / 32
+};
+#define QH_SORTED_ROWS 1024   // build rows a workgroup owns (4 per thread)
+#define QH_SORTED_MAX_WORDS 16384   // bitmap words one workgroup may own (64 per thread): more falls back to the atomic build
+template <class P, bool DEVROWS = false>
+__device__ __forceinline__ void qh_join_dense_build_sorted_body(const KArgs& a, const DenseSortedLaunch& L) {
+  constexpr u32 KM = 0x3FFFFFFFu, NULLKEY = 0x40000000u, INS = 0x80000000u;   // (key - kmin < n <= 2^30)
+  // the window: rows r0 - 1 .. r1 + 31 at positions 0 .. QH_SORTED_ROWS + 32 (position p = row r0 - 1 + p)
+  __shared__ u32 s_key[QH_SORTED_ROWS + 33];
+  const i64 nrows = DEVROWS ? qh_rows(a) : a.nrows;   // (a deferred-size build side: the pad rows behind the count take no part)
+  const i64 last_wg = nrows > 0 ? (nrows - 1) / QH_SORTED_ROWS : 0;
+  if ((i64)blockIdx.x > last_wg) return;   // (workgroup-uniform: the grid is sized from the capacity)
+  const i64 r0 = (i64)blockIdx.x * QH_SORTED_ROWS, base = r0 - 1;
+  const i64 r1 = r0 + QH_SORTED_ROWS < nrows ? r0 + QH_SORTED_ROWS : nrows;
+  const i64 wend = r1 + 32 < nrows ? r1 + 32 : nrows;
+  u32 err = 0, flags = 0;   // bit 0: key outside the range, bit 1: equal neighbours, bit 2: descent / NULL key
+  for (i64 i = (r0 > 0 ? base : r0) + (i64)threadIdx.x; i < wend; i += QH_BLOCK) {
+    u64 k[P::W];
+    u32 e = 0;
+    const u32 st = P::key_state(a, i, k, e);   // bit 0: the key is valid, bit 1: ... and the row passes the fused scan filter
+    const u64 idx = k[0] - L.kmin;
+    err |= (i >= r0 && i < r1) ? e : 0u;
+    u32 v;
+    if (!(st & 1u)) { v = NULLKEY; flags |= 4u; }
+    else if (idx >= (u64)L.n) { v = NULLKEY; flags |= 1u; }   // (cannot happen: the range comes from the column's own values)
+    else v = (u32)idx | ((st & 2u) ? INS : 0u);
+    s_key[i - base] = v;
+  }
+  __syncthreads();
+  for (i64 i = r0 + (i64)threadIdx.x; i < r1; i += QH_BLOCK) {
+    const u32 x = s_key[i - base];
+    if (i + 1 < nrows) {   // (the first row of the next range is in the window)
+      const u32 y = s_key[i + 1 - base];
+      // (equal neighbours are duplicate keys — unless a fused scan filter rejected one of them: the atomic dense build takes
+      // such a build side, only row_of[] cannot hold both rows, so that is a fallback and not a demotion to the CSR layout)
+      const bool both_in = (x & INS) && (y & INS);
+      flags |= (y & KM) == (x & KM) ? (both_in || !L.row_of ? 2u : 4u) : (y & KM) < (x & KM) ? 4u : 0u;
+    }
+    if (L.row_of && !(x & NULLKEY)) L.row_of[x & KM] = (u32)i;
+  }
+  // the words this workgroup owns: behind the previous range's last key .. up to its own last key (the last workgroup: all)
+  const u32 w_lo = r0 > 0 ? ((s_key[0] & KM) >> 5) + 1u : 0u;
+  u32 w_hi = (i64)blockIdx.x == last_wg ? L.words - 1u : ((s_key[r1 - 1 - base] & KM) >> 5);
+  w_hi = w_hi < L.words - 1u ? w_hi : L.words - 1u;
+  // a gap of more than QH_SORTED_MAX_WORDS words behind (or in front of) this range would be one workgroup's serial work —
+  // a subset whose value range is inherited from a much wider source column, say: the build falls back to the atomic form
+  // (the same signal as a descent: the host remembers the build side and runs the join again)
+  const bool too_wide = w_hi >= w_lo && w_hi - w_lo >= (u32)QH_SORTED_MAX_WORDS;
+  if (too_wide) flags |= 4u;
+  const u32 pend = (u32)(wend - base);   // positions [1, pend) = rows [r0, wend)
+  for (u32 w = w_lo + threadIdx.x; !too_wide && w <= w_hi; w += QH_BLOCK) {
+    const u32 v = w << 5;
+    u32 lo = 1, hi = pend;   // lower bound of v among the window's keys (ascending: the previous range's keys are all below v)
+    while (lo < hi) {
+      const u32 mid = (lo + hi) >> 1;
+      if ((s_key[mid] & KM) < v) lo = mid + 1; else hi = mid;
+    }
+    u32 bits = 0;
+    for (u32 p = lo; p < pend && p < lo + 32u; ++p) {
+      const u32 x = s_key[p];
+      const u32 d = (x & KM) - v;
+      if (d >= 32u) break;
+      bits |= (x & INS) ? 1u << d : 0u;
+    }
+    L.bits[w] = bits;
+    if (L.rank) L.rank[w] = (u32)(base + (i64)lo);
+  }
+  qh_report(L.status, err | ((flags & 1u) << QS_OVERFLOW));
+  const bool dup = qh_ballot((flags & 2u) != 0) != 0, broken = qh_ballot((flags & 4u) != 0) != 0;
+  if (qh_lane() == 0) {
+    if (dup && __hip_atomic_load(&L.status[QS_MAXCOUNT], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < 2u) atomicMax(&L.status[QS_MAXCOUNT], 2u);
+    if (broken) atomicOr(&L.status[QS_MAXCOUNT], (u32)QS_ORDER_BROKEN);
+  }
+}
+
+// The build row of a dense key (idx = key - kmin, its bit set): row_of[idx], or in the rank form of the sorted build
+// rank[w] + the set bits below idx in its word (two loads; the word is L2-warm from the probe). Clamped to `last` (the
+// build side's last row): an out-of-order build side that the host finds only after this read stays inside the table.
+__device__ __forceinline__ u32 qh_dense_build_row(const u32* row_of, const u32* rank, const u32* bits, u32 last, u32 idx) {
+  u32 b;
+  if (rank) {
+    const u32 w = idx >> 5;
+    b = rank[w] + (u32)__builtin_popcount(bits[w] & ((1u << (idx & 31u)) - 1u));
+  } else b = row_of[idx];
+  return b < last ? b : last;
+}
+
 // Probe pass 1 over the dense layout — software-pipelined over the wavefront's tiles like qh_join_probe_body, but with
 // THREE stages and nothing but column and bitmap loads in its steady state:
 //   stage 1  issue the column loads of tile t + 2
@@ -2159,7 +2273,10 @@ __device__ __forceinline__ void qh_dense_flush(const ProbeLaunch& L, QhDenseStag
     const u32 idx = st.idx[j];
     L.ent_slot[chunk_base + st.nflushed + j] = idx;
     L.ent_row[chunk_base + st.nflushed + j] = st.row[j];
-    if (L.visited) { const u32 b = ((const u32*)L.table)[idx]; atomicOr(&L.visited[b >> 5], 1u << (b & 31)); }
+    if (L.visited) {
+      const u32 b = qh_dense_build_row((const u32*)L.table, L.dense_rank, (const u32*)L.bloom, L.dense_last, idx);
+      atomicOr(&L.visited[b >> 5], 1u << (b & 31));
+    }
   }
   st.nflushed += st.nbuf;
   st.nbuf = 0;

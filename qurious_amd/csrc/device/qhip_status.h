@@ -12,3 +12,7 @@ enum {
   QS_MAXCOUNT = 7,       // value, not a flag: largest number of build rows sharing one join key
   QS_WORDS = 8
 };
+// flag bit of the status[QS_MAXCOUNT] word (not a count): a dense build that assumed strictly ascending build keys
+// (qh_join_dense_build_sorted_body) found them out of order, or a gap too wide for one workgroup — the host runs the join
+// again with the atomic dense build
+enum : unsigned { QS_ORDER_BROKEN = 1u << 30 };

@@ -1137,6 +1137,21 @@ int qhip_table_column_range(qhip_ctx* ctx, const qhip_table* t, int64_t col, int
   });
 }
 
+int qhip_table_column_ascending(qhip_ctx* ctx, const qhip_table* t, int64_t col, int32_t* out) {
+  if (!ctx || !t || !out || col < 0 || col >= (int64_t)t->cols.size()) return QHIP_INVALID_ARGUMENT;
+  return guarded(ctx, [&] {
+    QHIP_HIP_CHECK(hipSetDevice(ctx->device));
+    *out = key_ascending(ctx, t->cols[(size_t)col]) ? 1 : 0;
+  });
+}
+
+int qhip_ctx_sorted_build_counts(qhip_ctx* ctx, int64_t* launched, int64_t* fallbacks) {
+  if (!ctx || !launched || !fallbacks) return QHIP_INVALID_ARGUMENT;
+  *launched = ctx->sorted_builds;
+  *fallbacks = ctx->sorted_build_fallbacks;
+  return QHIP_OK;
+}
+
 int qhip_partition_filtered(qhip_ctx* ctx, const qhip_table* input, const qhip_expr* exprs, int32_t n_exprs, const int32_t* key_roots,
                             int32_t n_keys, int32_t predicate_root, const int32_t* keep_columns, int32_t n_parts, qhip_table** out_parts) {
   return qhip_partition_filtered_by_range(ctx, input, exprs, n_exprs, key_roots, n_keys, predicate_root, keep_columns, nullptr, n_parts, out_parts);

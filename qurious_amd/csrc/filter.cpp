@@ -124,6 +124,12 @@ static qhip_table* filter_execute(Ctx* ctx, const qhip_table* in, const qhip_exp
     out->cols[k] = gather_column(ctx, in->cols[(size_t)c], sel.as<uint32_t>(), m, false);
   }
   flush();
+  // a compaction keeps the order of what it keeps: a column that shares its source's value range shares its ascending order
+  for (size_t k = 0; k < cols.size(); ++k) {
+    const DevColumn& src = in->cols[(size_t)cols[k]];
+    DevColumn& oc = out->cols[k];
+    if (oc.range_inherited && oc.range == src.range && !src.deferred && !src.pending_upload) oc.range_order = !src.range_inherited || src.range_order;
+  }
   time_mark(ctx, 1);
   // output batch boundaries = kept rows before each input batch start
   const size_t nb1 = in->offsets().size();

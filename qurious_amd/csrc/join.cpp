@@ -77,7 +77,7 @@ qhip_table* hash_join(Ctx* ctx, const qhip_table* L, const qhip_table* R, int jo
   // build rows (default), 2 whenever the key qualifies (tests).
   // (g_dense_off: this join is being re-run after its dense table did not fit the device memory, see below)
   const int dense_mode = g_dense_off > 0 ? 0 : env_int("QHIP_JOIN_DENSE", 1);
-  bool dense_candidate = false;
+  bool dense_candidate = false, key_asc = false;
   int64_t kmin = 0, kmax = 0;
   uint64_t dense_n = 0;
   if (dense_mode != 0 && n_on == 1 && B > 0 && on_l[0] >= 0 && on_l[0] < nlex && lex[on_l[0]].kind == QHIP_EXPR_COLUMN && lex[on_l[0]].column >= 0 &&
@@ -93,6 +93,9 @@ qhip_table* hash_join(Ctx* ctx, const qhip_table* L, const qhip_table* R, int jo
       // the hashed layouts instead of failing the query.
       const uint64_t max_span = (uint64_t)1 << std::max(16, std::min(30, env_int("QHIP_JOIN_DENSE_MAX_SPAN_BITS", 28)));
       if (span < (1ULL << 30) && (dense_mode == 2 || (span < 256 * B + 65536 && span < max_span))) { dense_candidate = true; dense_n = span + 1; }
+      // strictly ascending build keys (found by the same reduction as the range, read through index vectors that keep the
+      // order): the dense build can then store every bitmap word once, without atomics (qh_join_dense_build_sorted_body)
+      key_asc = dense_candidate && key_ascending(ctx, kc);
     }
   }
   // the build key of a join over a join's output is a deferred gather: the dense build kernel reads it THROUGH the index
@@ -142,6 +145,17 @@ qhip_table* hash_join(Ctx* ctx, const qhip_table* L, const qhip_table* R, int jo
   const bool speculate = env_int("QHIP_JOIN_FORCE_CSR", 0) == 0 && env_int("QHIP_JOIN_NO_SPECULATION", 0) == 0 && !ctx->join_dup_builds.count(dup_hint);
   const int region_mode = env_int("QHIP_JOIN_REGION", 1);   // LDS-staged region build: 0 never, 1 when it pays, 2 always (tests)
   const bool dense = dense_candidate && speculate;   // (unique build keys assumed and checked, like the region build)
+  // The sorted form of the dense build (no atomics, no memset; the build keys' order is verified by the kernel and a build
+  // side found out of order is remembered by dup_hint and runs the atomic build from then on). QHIP_JOIN_DENSE_SORTED: 0
+  // never, 1 when the build key is known strictly ascending (default), 2 whenever the dense layout applies (tests).
+  // Rank form when every build row is inserted (no fused scan filter, no NULL keys): no row_of[] at all.
+  const int sorted_mode = env_int("QHIP_JOIN_DENSE_SORTED", 1);
+  const bool bytemap_wanted = env_int("QHIP_JOIN_DENSE_BYTEMAP", 0) != 0;
+  // (automatic mode: not when the bitmap words outnumber what the workgroups may own even on average — a subset of a much
+  // wider column; the kernel's own cap catches the uneven cases)
+  const bool sorted_fits = (dense_n + 31) / 32 <= std::max<uint64_t>(1, (B + kSortedBuildRows - 1) / kSortedBuildRows) * kSortedMaxWords;
+  const bool dense_sorted = dense && !bytemap_wanted && sorted_mode != 0 && (sorted_mode == 2 || (key_asc && sorted_fits)) &&
+                            !ctx->join_unsorted_builds.count(dup_hint);
   const bool want_regions = !dense && speculate && B > 0 && (region_mode == 2 || (region_mode == 1 && B >= 2048));
   // Deferred sizing (qhip.h: qhip_ctx_allow_deferred_sizes): this join as a whole is identified by both sides' expressions,
   // its type and the probe rows (the build rows too unless they are themselves a capacity)
@@ -191,6 +205,7 @@ qhip_table* hash_join(Ctx* ctx, const qhip_table* L, const qhip_table* R, int jo
     // the dense build's byte map, kept between executions: bytes[key - min] = the execution's stamp (1..255), so that it is
     // cleared once in 255 executions instead of every time (8x the bitmap's bytes: 60 MB for Q3's join 2)
     std::shared_ptr<DevBuf> bytemap; uint64_t bytemap_n = 0; uint32_t bytemap_gen = 0;
+    std::shared_ptr<Module> lmod_sorted;   // qk_join_dense_build_sorted of the build module
   };
   std::shared_ptr<JoinPlan> jp;
   {
@@ -258,7 +273,9 @@ qhip_table* hash_join(Ctx* ctx, const qhip_table* L, const qhip_table* R, int jo
   // k_join_region_build, the counts are not used)
   // (dense layout: table = u32 row_of[dense_n], never initialised — read only where the bitmap says a key is there; "filter"
   // = the exact bitmap, the only part that is cleared)
-  const size_t table_bytes = dense ? ((size_t)dense_n * 4 + 127) / 128 * 128 : (size_t)nslots * (1 + W) * 8;
+  // (rank form of the sorted dense build: table = u32 rank[dense_words] instead of row_of)
+  const bool dense_rank = dense_sorted && lpred < 0 && !lcols[(size_t)lex[on_l[0]].column].has_nulls;
+  const size_t table_bytes = dense_rank ? ((size_t)dense_words * 4 + 127) / 128 * 128 : dense ? ((size_t)dense_n * 4 + 127) / 128 * 128 : (size_t)nslots * (1 + W) * 8;
   const size_t count_bytes = (region_build || dense) ? 0 : (((size_t)nslots + 2) * 4 + 7) / 8 * 8;
   const size_t bloom_bytes = dense ? ((size_t)dense_words * 4 + 127) / 128 * 128 : (size_t)filter_words * 8;
   DevBuf arena;
@@ -274,7 +291,22 @@ qhip_table* hash_join(Ctx* ctx, const qhip_table* L, const qhip_table* R, int jo
   uint32_t* count = (uint32_t*)(arena.as<uint8_t>() + table_bytes);
   uint64_t* bloom = (uint64_t*)(arena.as<uint8_t>() + table_bytes + count_bytes);
   DevBuf start, row_slot, sorted_rows;
-  if (dense) {
+  if (dense_sorted) {
+    if (!jp->lmod_sorted) jp->lmod_sorted = get_module(ctx, lkp.source, "qk_join_dense_build_sorted");
+    HKArgs ka;
+    fill_kargs(ctx, L, lkp.bind, ka, jp->lstr);
+    HDenseSortedLaunch sl;
+    sl.bits = (uint32_t*)bloom; sl.status = dstat;
+    if (dense_rank) sl.rank = (uint32_t*)table; else sl.row_of = (uint32_t*)table;
+    sl.kmin = (uint64_t)kmin; sl.n = (uint32_t)dense_n; sl.words = dense_words;
+    void* args[] = {&ka, &sl};
+    // a workgroup per kSortedBuildRows build rows of the capacity (a deferred-size build side: the kernel reads the count)
+    const unsigned grid = (unsigned)std::max<uint64_t>(1, (B + kSortedBuildRows - 1) / kSortedBuildRows);
+    trace_point("join: first launch");
+    QHIP_HIP_CHECK(hipModuleLaunchKernel(jp->lmod_sorted->fn, grid, 1, 1, 256, 1, 1, 0, s, args, nullptr));
+    ++ctx->sorted_builds;
+    trace_point("join: first launch done");
+  } else if (dense) {
     if (!jp->lmod) jp->lmod = get_module(ctx, lkp.source, lkp.kernel_name);
     HKArgs ka;
     fill_kargs(ctx, L, lkp.bind, ka, jp->lstr);
@@ -360,7 +392,15 @@ qhip_table* hash_join(Ctx* ctx, const qhip_table* L, const qhip_table* R, int jo
   auto check_build_status = [&] {
     check_status_words(st_build);
     if (st_build[QS_OVERFLOW]) fail(QHIP_HIP_ERROR, "join build table overflow (internal error)");
-    max_count = st_build[QS_MAXCOUNT];
+    max_count = st_build[QS_MAXCOUNT] & ~(uint32_t)QS_ORDER_BROKEN;
+  };
+  // the sorted dense build found its keys out of order: remember the build side, run the join again with the atomic build
+  auto order_broken = [&] {
+    if (!dense_sorted || !(st_build[QS_MAXCOUNT] & QS_ORDER_BROKEN)) return false;
+    if (ctx->join_unsorted_builds.size() > 4096) ctx->join_unsorted_builds.clear();   // a hint, not a record
+    ctx->join_unsorted_builds.insert(dup_hint);
+    ++ctx->sorted_build_fallbacks;
+    return true;
   };
   if (!speculate) {
     QHIP_HIP_CHECK(hipMemcpyAsync(st_build, dstat, QS_WORDS * 4, hipMemcpyDeviceToHost, s));   // key evaluation + build
@@ -489,6 +529,7 @@ qhip_table* hash_join(Ctx* ctx, const qhip_table* L, const qhip_table* R, int jo
       pl.count = nullptr;
       pl.stage_cap = dense_lds ? stage_cap_lds : stage_cap_small;
       pl.dense_min = (uint64_t)kmin; pl.dense_n = (uint32_t)dense_n; pl.dense_words = dense_words; pl.lds_words = lds_words;
+      pl.dense_rank = dense_rank ? (const uint32_t*)table : nullptr; pl.dense_last = (uint32_t)(B - 1);
     }
     void* args[] = {&ka, &pl};
     time_mark(ctx, 2);
@@ -510,8 +551,9 @@ qhip_table* hash_join(Ctx* ctx, const qhip_table* L, const qhip_table* R, int jo
       rows_blk = std::make_shared<DevBuf>(64);   // the output table's device-side row count
       if (mat_key) key_vals = std::make_shared<DevBuf>((M + 1) * 8);
       // pass 2 also pads the index vectors up to the capacity, publishes the status block to `slot` and the total to rows_blk
-      launch_join_emit(ent_slot.as<uint32_t>(), ent_row.as<uint32_t>(), tile_nent.as<uint32_t>(), tile_tot.as<uint32_t>(), count, start_ptr, rows_ptr, dense ? (const uint32_t*)table : nullptr, nchunks, tiles_per_wave * kProbeTileRows, b_idx.as<uint32_t>(), p_idx.as<uint32_t>(),
-                       nullptr, nullptr, nullptr, (uint32_t)M, dstat, slot, rows_blk->as<uint32_t>(), s, key_vals ? key_vals->as<int64_t>() : nullptr, (uint64_t)kmin);
+      launch_join_emit(ent_slot.as<uint32_t>(), ent_row.as<uint32_t>(), tile_nent.as<uint32_t>(), tile_tot.as<uint32_t>(), count, start_ptr, rows_ptr, dense && !dense_rank ? (const uint32_t*)table : nullptr, nchunks, tiles_per_wave * kProbeTileRows, b_idx.as<uint32_t>(), p_idx.as<uint32_t>(),
+                       nullptr, nullptr, nullptr, (uint32_t)M, dstat, slot, rows_blk->as<uint32_t>(), s, key_vals ? key_vals->as<int64_t>() : nullptr, (uint64_t)kmin,
+                       dense_rank ? (const uint32_t*)table : nullptr, (const uint32_t*)bloom, dense ? (uint32_t)(B - 1) : 0xFFFFFFFFu);
       deferred_slot = slot;
     } else {
     // ONE read-back: build status (needed only now under speculation), probe status and the pair total
@@ -519,6 +561,7 @@ qhip_table* hash_join(Ctx* ctx, const qhip_table* L, const qhip_table* R, int jo
     QHIP_HIP_CHECK(sync_stream(s));
     verify_pending_sizes(ctx);   // (a build side of deferred size: did ITS join have room?)
     if (speculate) {
+      if (order_broken()) return hash_join(ctx, L, R, join_type, lex, nlex, rex, nrex, on_l, on_r, n_on, fex, nfex, froot, fsides, fcols, nfcols, lpred, rpred);
       check_build_status();
       if (max_count > 1) {   // duplicate build keys after all: remember, and run again with the CSR layout
         if (ctx->join_dup_builds.size() > 4096) ctx->join_dup_builds.clear();   // a hint, not a record
@@ -541,9 +584,10 @@ qhip_table* hash_join(Ctx* ctx, const qhip_table* L, const qhip_table* R, int jo
         QHIP_HIP_CHECK(hipMemsetAsync(cnt.ptr, 0, cnt.bytes, s));   // pass 2 only visits matching probe rows
       }
       if (mat_key) key_vals = std::make_shared<DevBuf>((M + 1) * 8);
-      launch_join_emit(ent_slot.as<uint32_t>(), ent_row.as<uint32_t>(), tile_nent.as<uint32_t>(), tile_tot.as<uint32_t>(), count, start_ptr, rows_ptr, dense ? (const uint32_t*)table : nullptr, nchunks, tiles_per_wave * kProbeTileRows, b_idx.as<uint32_t>(), p_idx.as<uint32_t>(),
+      launch_join_emit(ent_slot.as<uint32_t>(), ent_row.as<uint32_t>(), tile_nent.as<uint32_t>(), tile_tot.as<uint32_t>(), count, start_ptr, rows_ptr, dense && !dense_rank ? (const uint32_t*)table : nullptr, nchunks, tiles_per_wave * kProbeTileRows, b_idx.as<uint32_t>(), p_idx.as<uint32_t>(),
                        pad_right ? pair_off.as<uint32_t>() : nullptr, pad_right ? cnt.as<uint32_t>() : nullptr,
-                       mark_in_probe ? visited.as<uint32_t>() : nullptr, 0xFFFFFFFFu, nullptr, nullptr, nullptr, s, key_vals ? key_vals->as<int64_t>() : nullptr, (uint64_t)kmin);
+                       mark_in_probe ? visited.as<uint32_t>() : nullptr, 0xFFFFFFFFu, nullptr, nullptr, nullptr, s, key_vals ? key_vals->as<int64_t>() : nullptr, (uint64_t)kmin,
+                       dense_rank ? (const uint32_t*)table : nullptr, (const uint32_t*)bloom, dense ? (uint32_t)(B - 1) : 0xFFFFFFFFu);
     }
     }
     visited_done = mark_in_probe;
@@ -654,16 +698,19 @@ qhip_table* hash_join(Ctx* ctx, const qhip_table* L, const qhip_table* R, int jo
   const bool left_nullable = pad_right;
   const bool right_nullable = has_tail;
   const bool eager = env_int("QHIP_EAGER_GATHER", 0) != 0;
-  auto add_side = [&](const qhip_table* src, const std::shared_ptr<DevBuf>& idx, bool side_nullable) {
+  // (an Inner join with unique build keys emits its pairs in probe-row order, one per probe row at most: the probe side's
+  // index vector ascends strictly, and a key column read through it keeps its order — key_ascending)
+  const bool probe_idx_ascends = join_type == QHIP_JOIN_INNER && unique_keys && T == 0;
+  auto add_side = [&](const qhip_table* src, const std::shared_ptr<DevBuf>& idx, bool side_nullable, bool idx_ascends) {
     if (eager) for (auto& c : src->cols) out->cols.push_back(gather_column(ctx, c, idx->as<uint32_t>(), total_rows, side_nullable));
-    else defer_gather(ctx, src->cols, idx, total_rows, side_nullable, out->cols);
+    else defer_gather(ctx, src->cols, idx, total_rows, side_nullable, out->cols, idx_ascends);
     for (size_t c = 0; c < src->cols.size(); ++c) {
       out->names.push_back(src->names[c]);
       out->nullable.push_back(src->nullable[c] || side_nullable);
     }
   };
-  add_side(L, b_all, left_nullable);
-  if (!semi_anti) add_side(R, p_all, right_nullable);
+  add_side(L, b_all, left_nullable, false);
+  if (!semi_anti) add_side(R, p_all, right_nullable, probe_idx_ascends);
   if (key_vals) {
     auto plain = [&](const DevColumn& src) {
       DevColumn c;

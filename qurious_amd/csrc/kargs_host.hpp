@@ -94,8 +94,10 @@ struct HProbeLaunch {
   uint32_t tiles_per_wave = 1, lds_words = 0;
   uint64_t dense_min = 0;                        // dense (direct-address) layout: bloom = exact bitmap, table = u32 row_of[]
   uint32_t dense_n = 0, dense_words = 0;
+  const uint32_t* dense_rank = nullptr;          // rank form of the sorted dense build (no row_of), else null
+  uint32_t dense_last = 0, pad_ = 0;             // the build side's last row
 };
-static_assert(sizeof(HProbeLaunch) == 11 * 8 + 8 + 16 + 8 + 16, "ProbeLaunch layout");
+static_assert(sizeof(HProbeLaunch) == 11 * 8 + 8 + 16 + 8 + 16 + 16, "ProbeLaunch layout");
 
 struct HDenseBuildLaunch {
   uint32_t* bits;
@@ -108,6 +110,19 @@ struct HDenseBuildLaunch {
   uint32_t* counters = nullptr;
 };
 static_assert(sizeof(HDenseBuildLaunch) == 56, "DenseBuildLaunch layout");
+
+struct HDenseSortedLaunch {
+  uint32_t* bits;
+  uint32_t* rank = nullptr;
+  uint32_t* row_of = nullptr;
+  uint32_t* status;
+  uint64_t kmin;
+  uint32_t n;
+  uint32_t words;
+};
+static_assert(sizeof(HDenseSortedLaunch) == 48, "DenseSortedLaunch layout");
+constexpr uint64_t kSortedBuildRows = 1024;   // QH_SORTED_ROWS: build rows per workgroup of qk_join_dense_build_sorted
+constexpr uint64_t kSortedMaxWords = 16384;   // QH_SORTED_MAX_WORDS: bitmap words one of its workgroups may own
 
 struct HPartIdsLaunch {
   uint8_t* ids;

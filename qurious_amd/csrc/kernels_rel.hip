@@ -383,17 +383,25 @@ __global__ __launch_bounds__(QH_BLOCK) void k_narrow_decimal(const u64* v, u64 n
 // ~(v ^ sign bit), i.e. the order-preserving unsigned images of max and min, both gathered with atomic max from zero-filled
 // words (one atomic pair per wavefront, none when it would change nothing). NULL slots take part with whatever their value
 // slot holds: the range may only be wider for it. Decides whether a hash join can address its table by the key itself.
+// out[2] != 0: some value is not below its successor (the column is not strictly ascending — the sorted dense build needs
+// that; the host counts a column with NULLs as not ascending whatever this says). The successor is the next lane's value or
+// one load that hits the same line.
 template <class T>
 __global__ __launch_bounds__(QH_BLOCK) void k_value_range(const T* v, u64 n, u64* out) {
   u64 hi = 0, lo = 0;
+  bool descent = false;
   for (u64 i = (u64)blockIdx.x * QH_BLOCK + threadIdx.x; i < n; i += (u64)gridDim.x * QH_BLOCK) {
-    const u64 img = (u64)(i64)v[i] ^ 0x8000000000000000ULL;
+    const i64 x = (i64)v[i];
+    const u64 img = (u64)x ^ 0x8000000000000000ULL;
     hi = img > hi ? img : hi;
     lo = ~img > lo ? ~img : lo;
+    if (i + 1 < n) descent = descent || !(x < (i64)v[i + 1]);
   }
   hi = qh_wave_max_u64(hi);
   lo = qh_wave_max_u64(lo);
+  const bool any_descent = qh_ballot(descent) != 0;
   if (qh_lane() == 0) {
+    if (any_descent && !__hip_atomic_load(&out[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) (void)__hip_atomic_fetch_max(&out[2], (u64)1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (hi > __hip_atomic_load(&out[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) (void)__hip_atomic_fetch_max(&out[0], hi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (lo > __hip_atomic_load(&out[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) (void)__hip_atomic_fetch_max(&out[1], lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
@@ -621,7 +629,8 @@ __global__ __launch_bounds__(QH_BLOCK) void k_bytes_to_bits(const u8* bytes, u32
 __global__ __launch_bounds__(QH_BLOCK) void k_join_emit(const u32* ent_slot, const u32* ent_row, const u32* chunk_nent, const u32* chunk_off,
                                                        const u32* count, const u32* start, const u32* rows, const u32* row_of, u64 nchunks, u64 chunk_rows, u32* b_idx,
                                                        u32* p_idx, u32* pair_off, u32* cnt_out, u32* visited, u32 cap, const u32* stat_block,
-                                                       u32* publish, u32* rows_out, i64* key_out, u64 key_min) {
+                                                       u32* publish, u32* rows_out, i64* key_out, u64 key_min, const u32* rank, const u32* rank_bits,
+                                                       u32 build_last) {
   // a join of deferred size (cap = the room its output has; stat_block = [build status | probe status | pair total]): rows
   // [total, cap) of the index vectors repeat row 0 of both sides (valid to gather, never counted), the total goes to the
   // output table's device-side row count and the status block to page-locked host memory, where the consumer's
@@ -664,9 +673,9 @@ __global__ __launch_bounds__(QH_BLOCK) void k_join_emit(const u32* ent_slot, con
             if (live[u] && o < cap) key_out[o] = (i64)(key_min + (u64)sid[u]);
           }
         }
-        if (row_of) {
+        if (row_of || rank) {
 #pragma unroll
-          for (int u = 0; u < 4; ++u) sid[u] = live[u] ? row_of[sid[u]] : 0u;
+          for (int u = 0; u < 4; ++u) sid[u] = live[u] ? qh_dense_build_row(row_of, rank, rank_bits, build_last, sid[u]) : 0u;
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
@@ -683,7 +692,7 @@ __global__ __launch_bounds__(QH_BLOCK) void k_join_emit(const u32* ent_slot, con
       const u32 p = live ? ent_row[e0 + j] : 0u;
       // dense (direct-address) layout: the entry holds key - min; the build row is looked up HERE, for the matching rows only
       // (qh_join_probe_dense_body keeps the lookup out of its streaming loop)
-      if (row_of && live) sid = row_of[sid];
+      if ((row_of || rank) && live) sid = qh_dense_build_row(row_of, rank, rank_bits, build_last, sid);
       u32 c = start ? count[sid] : 1u;
       c = live ? c : 0u;
       const u32 incl = wave_incl_scan_u32(c);
@@ -1324,12 +1333,13 @@ void launch_bytes_to_bits(const uint8_t* bytes, uint32_t gen, uint32_t* bits, ui
 void launch_join_emit(const uint32_t* ent_slot, const uint32_t* ent_row, const uint32_t* chunk_nent, const uint32_t* chunk_off, const uint32_t* count,
                       const uint32_t* start, const uint32_t* rows, const uint32_t* row_of, uint64_t nchunks, uint64_t chunk_rows, uint32_t* b_idx, uint32_t* p_idx,
                       uint32_t* pair_off, uint32_t* cnt_out, uint32_t* visited, uint32_t cap, const uint32_t* stat_block, uint32_t* publish,
-                      uint32_t* rows_out, hipStream_t s, int64_t* key_out, uint64_t key_min) {
+                      uint32_t* rows_out, hipStream_t s, int64_t* key_out, uint64_t key_min, const uint32_t* rank, const uint32_t* rank_bits,
+                      uint32_t build_last) {
   if (!nchunks) return;
   hipLaunchKernelGGL(k_join_emit, dim3(grid_for(nchunks * 64, QH_BLOCK)), dim3(QH_BLOCK), 0, s, (const u32*)ent_slot, (const u32*)ent_row,
                      (const u32*)chunk_nent, (const u32*)chunk_off, (const u32*)count, (const u32*)start, (const u32*)rows, (const u32*)row_of, (u64)nchunks,
                      (u64)chunk_rows, (u32*)b_idx, (u32*)p_idx, (u32*)pair_off, (u32*)cnt_out, (u32*)visited, (u32)cap, (const u32*)stat_block,
-                     (u32*)publish, (u32*)rows_out, (i64*)key_out, (u64)key_min);
+                     (u32*)publish, (u32*)rows_out, (i64*)key_out, (u64)key_min, (const u32*)rank, (const u32*)rank_bits, (u32)build_last);
 }
 void launch_join_mark(const uint32_t* b_idx, const uint32_t* p_idx, uint64_t m, uint32_t* visited_bits, uint32_t* cnt_per_probe, hipStream_t s) {
   if (!m) return;

@@ -350,14 +350,15 @@ bool key_range_of(Ctx* ctx, const DevColumn& col_in, int64_t& mn, int64_t& mx) {
         base->range = std::make_shared<ColRange>();
         base->range_inherited = false;
       }
-      DevBuf out(16);
-      QHIP_HIP_CHECK(hipMemsetAsync(out.ptr, 0, 16, ctx->stream));
+      DevBuf out(24);   // [max image | ~min image | some value not below its successor]
+      QHIP_HIP_CHECK(hipMemsetAsync(out.ptr, 0, 24, ctx->stream));
       const bool is_signed = !(base->type.id == QHIP_UINT8 || base->type.id == QHIP_UINT16 || base->type.id == QHIP_UINT32 || base->type.id == QHIP_UINT64);
       launch_value_range(base->values->ptr, (uint64_t)base->length, w, is_signed, out.as<uint64_t>(), ctx->stream);
-      uint64_t h[2] = {0, 0};
-      copy_sync(ctx->stream, h, out.ptr, 16, hipMemcpyDeviceToHost);
+      uint64_t h[3] = {0, 0, 0};
+      copy_sync(ctx->stream, h, out.ptr, 24, hipMemcpyDeviceToHost);
       base->range->max = (int64_t)(h[0] ^ 0x8000000000000000ULL);
       base->range->min = (int64_t)(~h[1] ^ 0x8000000000000000ULL);
+      base->range->ascending = h[2] == 0 && base->null_count == 0;
       base->range->known = true;
     }
     if (base != col) { col->range = base->range; col->range_inherited = true; }
@@ -365,6 +366,22 @@ bool key_range_of(Ctx* ctx, const DevColumn& col_in, int64_t& mn, int64_t& mx) {
   mn = col->range->min;
   mx = col->range->max;
   return true;
+}
+
+// Strictly ascending values (ColRange::ascending, found by key_range_of's reduction) — valid for the column that computed
+// it, and for a subset of it only when the subset keeps the order: a deferred gather through an ascending index vector
+// (DeferredGather::idx_ascends) or a column marked DevColumn::range_order (a Filter's compaction, a resolved such gather).
+// The ColRange object is shared with every subset, so the flag itself never travels on its own.
+bool key_ascending(Ctx* ctx, const DevColumn& col) {
+  int64_t mn = 0, mx = 0;
+  if (!key_range_of(ctx, col, mn, mx)) return false;
+  if (col.deferred && !col.deferred->done) {
+    const DeferredGather& d = *col.deferred;
+    return d.idx_ascends && !d.idx_may_be_null && d.src.range->known && d.src.range->ascending &&
+           (!d.src.range_inherited || d.src.range_order);
+  }
+  const DevColumn& c = resolved(ctx, col);
+  return c.range->known && c.range->ascending && c.null_count == 0 && (!c.range_inherited || c.range_order);
 }
 
 DevColumn materialize_upload(Ctx* ctx, const DeferredUpload& u);   // table.cpp
@@ -386,6 +403,7 @@ const DevColumn& resolved(Ctx* ctx, const DevColumn& col) {
   DeferredGather& d = *col.deferred;
   if (!d.done) {
     d.result = gather_column(ctx, d.src, d.idx->as<uint32_t>(), d.m, d.idx_may_be_null);
+    d.result.range_order = d.idx_ascends && !d.idx_may_be_null && (!d.src.range_inherited || d.src.range_order);
     d.done = true;
     d.src = DevColumn();   // the source buffers and the index vector are no longer needed by this column
     d.idx.reset();
@@ -404,7 +422,7 @@ void resolve_all(Ctx* ctx, const qhip_table* t) {
 }
 
 void defer_gather(Ctx* ctx, const std::vector<DevColumn>& cols, const std::shared_ptr<DevBuf>& idx, uint64_t m, bool idx_may_be_null,
-                  std::vector<DevColumn>& out) {
+                  std::vector<DevColumn>& out, bool idx_ascends) {
   std::vector<std::pair<const DevBuf*, std::shared_ptr<DevBuf>>> composed;   // inner index vector -> inner[idx]
   // the compositions (one per distinct inner index vector) go into ONE launch
   {
@@ -445,11 +463,13 @@ void defer_gather(Ctx* ctx, const std::vector<DevColumn>& cols, const std::share
       d->src = in.src;
       d->idx = both;
       d->idx_may_be_null = in.idx_may_be_null || idx_may_be_null;
+      d->idx_ascends = in.idx_ascends && idx_ascends;   // (an ascending vector read through an ascending one ascends)
     } else {
       d->src = c.deferred ? c.deferred->result : c;
       d->src.deferred.reset();
       d->idx = idx;
       d->idx_may_be_null = idx_may_be_null;
+      d->idx_ascends = idx_ascends;
     }
     o.null_count = (d->src.null_count > 0 || d->idx_may_be_null) ? 1 : 0;
     if (d->src.type.id == QHIP_NULL) o.null_count = (int64_t)m;
@@ -499,6 +519,7 @@ void resolve_referenced(Ctx* ctx, const qhip_table* t, const qhip_expr* exprs, i
         out.utf8_max_len = d.src.utf8_max_len;
         out.value_maxabs = d.src.value_maxabs;
         out.range = d.src.range; out.range_inherited = true;   // (a subset's values lie inside its source's range)
+        out.range_order = d.idx_ascends && !d.idx_may_be_null && (!d.src.range_inherited || d.src.range_order);
         const int w = dtype_width(d.src.type);
         out.values = std::make_shared<DevBuf>((size_t)d.m * (size_t)w);
         gb.d[j] = GatherDesc{d.src.values->ptr, d.idx->as<uint32_t>(), out.values->ptr, d.m, (uint32_t)w, 0u};

@@ -35,7 +35,7 @@ const DevColumn& resolved(Ctx* ctx, const DevColumn& col);
 // Deferred out[k] = col[idx[k]] for every column of `cols`, appended to `out`: nothing is gathered until a column is
 // read. Deferred inputs are composed (one u32 gather per distinct inner index vector), never chained.
 void defer_gather(Ctx* ctx, const std::vector<DevColumn>& cols, const std::shared_ptr<DevBuf>& idx, uint64_t m, bool idx_may_be_null,
-                  std::vector<DevColumn>& out);
+                  std::vector<DevColumn>& out, bool idx_ascends = false);
 void resolve_all(Ctx* ctx, const qhip_table* t);
 // gather the columns the expression trees reference (everything else may stay deferred)
 void resolve_referenced(Ctx* ctx, const qhip_table* t, const qhip_expr* exprs, int n_exprs, bool keep_indirect = false);
@@ -53,6 +53,7 @@ void ensure_narrow_int_columns(Ctx* ctx, const qhip_table* t, const qhip_expr* e
 // [mn, mx] of an integer-like column's values (cached on the column and shared with its source table, DevColumn::range);
 // false when the column has no values to look at / is not integer-like
 bool key_range_of(Ctx* ctx, const DevColumn& col, int64_t& mn, int64_t& mx);
+bool key_ascending(Ctx* ctx, const DevColumn& col);   // strictly ascending values, through the index vectors that keep the order
 // key words [W][N] + validity bitmap of the key expressions `roots`
 void eval_key_words(Ctx* ctx, const qhip_table* t, const ExprSet& es, const std::vector<InputCol>& icols, const int32_t* roots, int n,
                     KeysPlan& kp, DevBuf& keys, DevBuf& keyvalid, int predicate_root = -1, bool deferred_status = false,

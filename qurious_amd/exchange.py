@@ -284,6 +284,27 @@ def column_range(table: DeviceTable, col: int) -> Tuple[int, int]:
     return int(lo.value), int(hi.value)
 
 
+def column_ascending(table: DeviceTable, col: int) -> bool:
+    """qhip_table_column_ascending: whether a column is known strictly ascending (through order-keeping index vectors only)"""
+    ctx = table.ctx
+    fn = ctx.lib.qhip_table_column_ascending
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int32)]
+    out = C.c_int32()
+    ctx.check(fn(ctx.handle, table.handle, int(col), C.byref(out)))
+    return bool(out.value)
+
+
+def sorted_build_counts(ctx) -> Tuple[int, int]:
+    """qhip_ctx_sorted_build_counts: (sorted dense join builds launched, of those found out of order and run again)"""
+    fn = ctx.lib.qhip_ctx_sorted_build_counts
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    a, b = C.c_int64(), C.c_int64()
+    ctx.check(fn(ctx.handle, C.byref(a), C.byref(b)))
+    return int(a.value), int(b.value)
+
+
 class qhip_shuffle_input(C.Structure):
     _fields_ = [("table", C.c_void_p), ("exprs", C.POINTER(_ffi.qhip_expr)), ("n_exprs", C.c_int32), ("key_roots", C.POINTER(C.c_int32)),
                 ("n_keys", C.c_int32), ("predicate_root", C.c_int32), ("all_gather", C.c_int32), ("keep_columns", C.POINTER(C.c_int32)),
