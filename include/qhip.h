@@ -123,9 +123,18 @@ typedef enum qhip_expr_kind {
   QHIP_EXPR_NEGATIVE = 6, /* negative.rs       : child `left` */
   QHIP_EXPR_IF = 7,       /* case.rs:33-48     : zip(mask = `left`, truthy = `right`, falsy = `third`); CASE WHEN c1 THEN v1
                            *                      WHEN c2 THEN v2 ELSE e END is lowered as IF(c1, v1, IF(c2, v2, e)) */
-  QHIP_EXPR_LIKE = 8      /* like.rs:28-43     : `left` LIKE `right` (a Utf8 literal pattern: % _ and \ escapes);
+  QHIP_EXPR_LIKE = 8,     /* like.rs:28-43     : `left` LIKE `right` (a Utf8 literal pattern: % _ and \ escapes);
                            *                      op != 0 = NOT LIKE */
+  QHIP_EXPR_FUNCTION = 9  /* function.rs       : built-in function `op` (qhip_function) over its arguments in the reference's
+                           *                      order: `left` (arg 0) then `right` (arg 1) then `third` (arg 2); -1 after the
+                           *                      last argument (more than three arguments cannot be expressed) */
 } qhip_expr_kind;
+
+/* functions/mod.rs all_builtin_functions() */
+typedef enum qhip_function {
+  QHIP_FN_EXTRACT = 0     /* functions/datetime/extract.rs: EXTRACT(part FROM x); arg 0 the part as a Utf8 literal, arg 1 a
+                           * Date32 / Date64 / Timestamp(unit; no time zone) -> nullable Int64 */
+} qhip_function;
 
 /* One node of an expression tree stored as a flat array; children are indices
  * into the same array (-1 = none). Literals: integers/dates/bools in lit_lo

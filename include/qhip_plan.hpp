@@ -182,6 +182,35 @@ struct Like : PhysicalExpr {   // like.rs:14-43
   std::string to_string() const override { return expr->to_string() + (negated ? " NOT LIKE " : " LIKE ") + pattern->to_string(); }
 };
 
+// functions/mod.rs:9-24: built-in functions, evaluated inside the generated kernels (qhip_function)
+struct UserDefinedFunction {
+  virtual ~UserDefinedFunction() = default;
+  virtual std::string name() const = 0;
+  virtual qhip_dtype return_type() const = 0;
+  virtual bool is_nullable() const { return true; }
+  virtual int id() const = 0;
+};
+struct DatetimeExtract : UserDefinedFunction {   // functions/datetime/extract.rs: EXTRACT(part FROM x), args [Utf8 part, x]
+  std::string name() const override { return "EXTRACT"; }
+  qhip_dtype return_type() const override { return dtype(QHIP_INT64); }
+  int id() const override { return QHIP_FN_EXTRACT; }
+};
+using FunctionRef = std::shared_ptr<const UserDefinedFunction>;
+struct Function : PhysicalExpr {   // physical/expr/function.rs: the arguments ride in the three child slots, in order
+  FunctionRef func; std::vector<ExprRef> args;
+  Function(FunctionRef f, std::vector<ExprRef> a) : func(std::move(f)), args(std::move(a)) {
+    if (args.size() > 3) throw Error(QHIP_INVALID_ARGUMENT, func->name() + " requires 2 arguments");
+  }
+  int lower(ExprArray& o) const override {
+    int slot[3] = {-1, -1, -1};
+    for (size_t k = 0; k < args.size(); ++k) slot[k] = args[k]->lower(o);
+    qhip_expr e = ExprArray::node(QHIP_EXPR_FUNCTION);
+    e.op = func->id(); e.left = slot[0]; e.right = slot[1]; e.third = slot[2];
+    return o.add(e);
+  }
+  std::string to_string() const override { return func->name(); }
+};
+
 // physical/expr/aggregate/{sum,avg,count,min,max}.rs
 struct AggregateExpr {
   int kind; ExprRef expr; qhip_dtype return_type;

@@ -8,8 +8,9 @@ ROCm runtime (/opt/rocm/lib); a later ``import torch`` then shares that runtime 
 from ._ffi import (ArrowError, Context, DeviceTable, HipError, InternalError, QuriousError, UnsupportedError,  # noqa: F401
                    get_context, load_library)
 from .datatypes import JoinSide, JoinType, Operator, ScalarValue  # noqa: F401
-from .expr import (AvgAggregateExpr, BinaryExpr, CaseExpr, CastExpr, Column, CountAggregateExpr, IsNotNull, IsNull,  # noqa: F401
+from .expr import (AvgAggregateExpr, BinaryExpr, CaseExpr, CastExpr, Column, CountAggregateExpr, Function, IsNotNull, IsNull,  # noqa: F401
                    Like, Literal, MaxAggregateExpr, MinAggregateExpr, Negative, PhysicalExpr, SumAggregateExpr, avg_return_type)
+from .functions import DatetimeExtract, UserDefinedFunction, all_builtin_functions  # noqa: F401
 from .planner import DefaultQueryPlanner  # noqa: F401
 from .datasource import CsvReadOptions, read_csv, read_json, read_parquet  # noqa: F401
 from .plan import (CrossJoin, Filter, HashAggregate, HashJoinExec, JoinFilter, Limit, MemoryTable, NestedLoopJoinExec,  # noqa: F401

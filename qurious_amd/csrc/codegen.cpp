@@ -482,6 +482,18 @@ void ExprGen::emit(int k, std::string& out) {
         << len(n.left) << ", a.strlit + a.stroff[" << s << "], a.stroff[" << s + 1 << "] - a.stroff[" << s << "]);\n";
       break;
     }
+    case QHIP_EXPR_FUNCTION: {
+      // EXTRACT(part FROM x): the part (and the argument's unit) are constants of the source, so qh_dt_extract
+      // (device/qhip_datetime.inc) folds to the one path it needs; a row outside chrono's range is NULL
+      emit(n.right, out);
+      const ENode& x = es_.at(n.right);
+      const int unit = x.type.id == QHIP_DATE32 ? -1 : x.type.id == QHIP_TIMESTAMP_S ? 0 : x.type.id == QHIP_TIMESTAMP_US ? 6
+                     : x.type.id == QHIP_TIMESTAMP_NS ? 9 : 3;
+      o << "    i64 " << v << "; const bool r" << K << " = qh_dt_extract(" << n.dt_part << ", " << unit << ", (i64)" << val(n.right) << ", " << v << ");\n";
+      if (n.nullable) o << "    const bool " << nn << " = " << ok(n.right) << " && r" << K << ";\n";
+      else o << "    (void)r" << K << ";\n";
+      break;
+    }
     case QHIP_EXPR_NEGATIVE: {
       emit(n.left, out);
       if (n.nullable) o << "    const bool " << nn << " = " << ok(n.left) << ";\n";

@@ -70,6 +70,9 @@ __device__ __forceinline__ double qh_f64(u64 bits) { return __longlong_as_double
 __device__ __forceinline__ u64 qh_f64_ord(double d) { u64 b = (u64)__double_as_longlong(d); return (b >> 63) ? ~b : (b | 0x8000000000000000ULL); }
 __device__ __forceinline__ double qh_ord_f64(u64 k) { u64 b = (k >> 63) ? (k & 0x7fffffffffffffffULL) : ~k; return __longlong_as_double((i64)b); }
 
+// EXTRACT(part FROM date / timestamp): civil date, ISO week, timestamp split, chrono's range (shared with the host's folding)
+#include "qhip_datetime.inc"
+
 // Utf8 value of at most 7 bytes packed injectively into one key word: byte 7 = length, bytes 0..len-1 = data.
 // Branch-free: one unaligned 8-byte load (every Utf8 data buffer is allocated with >= 8 bytes of slack), masked to
 // the value's length; a loop of byte loads would put control flow between the loads of a tile's rows.

@@ -8,6 +8,8 @@
 #include <cstdlib>
 #include <limits>
 
+#include "device/qhip_datetime.inc"   // (plain host C++ here: the same date code the kernels run)
+
 namespace qhip {
 
 i128 pow10_i128(int e) {
@@ -179,6 +181,28 @@ std::string canonical_like_pattern(const std::string& p) {
   return out;
 }
 
+// EXTRACT parts in QH_DT_* order (the canonical form's suffix) and |value| bounds: year within chrono's range
+static const char* const kDtParts[] = {"year", "month", "day", "hour", "minute", "second", "week"};
+static const int kDtMaxAbs[] = {262144, 12, 31, 23, 59, 59, 53};
+
+static int extract_unit(const DType& t) {
+  switch (t.id) {
+    case QHIP_DATE32: return -1;
+    case QHIP_TIMESTAMP_S: return 0;
+    case QHIP_DATE64: case QHIP_TIMESTAMP_MS: return 3;
+    case QHIP_TIMESTAMP_US: return 6;
+    case QHIP_TIMESTAMP_NS: return 9;
+    default: return -2;
+  }
+}
+
+bool extract_value(int part, const DType& arg_type, int64_t v, int64_t& out) {
+  long long r = 0;
+  const bool ok = qh_dt_extract(part, extract_unit(arg_type), (long long)v, r);
+  out = (int64_t)r;
+  return ok;
+}
+
 static bool device_cast_supported(const DType& from, const DType& to) {
   if (from == to) return true;
   auto numeric = [](const DType& t) { return is_intlike(t) || dtype_is_float(t) || t.id == QHIP_DECIMAL128; };
@@ -325,6 +349,42 @@ void ExprSet::build(const qhip_expr* ex, int n, const std::vector<InputCol>& inp
         nd.canon = std::string(e.op ? "nlike(" : "like(") + x.canon + "," + pat.canon + ")";
         break;
       }
+      case QHIP_EXPR_FUNCTION: {
+        // functions/datetime/extract.rs: Function(DatetimeExtract, [part, x]) -> date_part(x, part) cast to Int64
+        if (e.op != QHIP_FN_EXTRACT) fail(QHIP_INVALID_ARGUMENT, "unknown function id " + std::to_string(e.op));
+        if (e.left < 0 || e.right < 0 || e.third >= 0) fail(QHIP_INVALID_ARGUMENT, "EXTRACT requires 2 arguments");
+        visit(e.left); visit(e.right);
+        const ENode &part = nodes[(size_t)e.left], &x = nodes[(size_t)e.right];
+        // the reference applies row 0's part to every row: only a literal is the same for all rows
+        if (part.kind != QHIP_EXPR_LITERAL || (part.type.id != QHIP_UTF8 && !part.lit_null))
+          fail(QHIP_UNSUPPORTED, "EXTRACT with a part that is not a Utf8 literal is not accelerated");
+        if (part.lit_null) fail(QHIP_INVALID_ARGUMENT, "First argument of `EXTRACT` must be non-null scalar Utf8");
+        std::string unit = part.s;
+        for (char& c : unit) if (c >= 'A' && c <= 'Z') c = (char)(c - 'A' + 'a');
+        if (unit == "century" || unit == "decade") fail(QHIP_INVALID_ARGUMENT, "Date part '" + unit + "' not supported");
+        int p = -1;
+        for (int k = 0; k < (int)(sizeof kDtParts / sizeof kDtParts[0]); ++k) if (unit == kDtParts[k]) p = k;
+        if (p < 0) fail(QHIP_UNSUPPORTED, "EXTRACT(" + unit + " FROM ...) is not accelerated");
+        if (extract_unit(x.type) < -1) fail(QHIP_UNSUPPORTED, "EXTRACT from " + dtype_name(x.type) + " is not accelerated");
+        if (x.kind == QHIP_EXPR_LITERAL) {
+          // evaluated once on the host with the kernels' date code, becomes a kernel scalar (like fold_literal_cast)
+          nd = ENode();
+          nd.kind = QHIP_EXPR_LITERAL;
+          nd.type = DType(QHIP_INT64);
+          int64_t r = 0;
+          nd.lit_null = x.lit_null || !extract_value(p, x.type, (int64_t)x.lo, r);
+          nd.nullable = nd.lit_null;
+          nd.lo = nd.lit_null ? 0 : (uint64_t)r;
+          nd.hi = -(int64_t)(nd.lo >> 63);
+          break;
+        }
+        nd.type = DType(QHIP_INT64);
+        nd.dt_part = p;
+        // NULL where the argument is, and outside chrono's range (never for the constant time parts of a Date32)
+        nd.nullable = (x.type.id == QHIP_DATE32 && qh_dt_date32_zero_part(p)) ? x.nullable : true;
+        nd.canon = std::string("extract[") + kDtParts[p] + "](" + x.canon + ")";
+        break;
+      }
       default:
         fail(QHIP_INVALID_ARGUMENT, "unknown expression kind " + std::to_string(e.kind));
     }
@@ -372,6 +432,8 @@ void ExprSet::build(const qhip_expr* ex, int n, const std::vector<InputCol>& inp
         } else if (nd.kind == QHIP_EXPR_IF) {
           const u128 a = nodes[(size_t)nd.right].maxabs, b = nodes[(size_t)nd.third].maxabs;
           nd.maxabs = a > b ? a : b;
+        } else if (nd.kind == QHIP_EXPR_FUNCTION) {
+          nd.maxabs = (u128)kDtMaxAbs[nd.dt_part];
         }
       }
     }

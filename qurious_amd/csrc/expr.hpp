@@ -19,6 +19,7 @@ struct ENode {
   double f = 0;
   std::string s;
   DType cast_to;           // CAST target
+  int dt_part = -1;        // EXTRACT: the part (QH_DT_*, device/qhip_datetime.inc), resolved once from the literal
   std::string canon;       // structural identity (for common-subexpression sharing)
   // upper bound of |value| over all rows for integer / Decimal128 nodes (the unscaled integer), from the columns' cached
   // statistics, the literals' values and the operators; kUnbounded = nothing better than the type is known
@@ -55,6 +56,8 @@ struct ExprSet {
 void fold_literal_cast(const ENode& src, const DType& to, ENode& out);
 int32_t parse_date32(const std::string& s);   // "YYYY-MM-DD" -> days since epoch; throws QHIP_EXEC_ERROR
 i128 pow10_i128(int e);
+// EXTRACT of one value on the host with the device's date code (literal folding): false = NULL
+bool extract_value(int part, const DType& arg_type, int64_t v, int64_t& out);
 // LIKE pattern -> matcher tokens: literal bytes, 0xFF for %, 0xFE for _ (neither byte occurs in UTF-8); `\\x` -> x
 std::string canonical_like_pattern(const std::string& pattern);
 

@@ -12,7 +12,7 @@ from . import _ffi
 from .datatypes import Operator, ScalarValue, to_qhip_dtype
 
 # qhip_expr_kind
-K_COLUMN, K_LITERAL, K_BINARY, K_CAST, K_IS_NULL, K_IS_NOT_NULL, K_NEGATIVE, K_IF, K_LIKE = range(9)
+K_COLUMN, K_LITERAL, K_BINARY, K_CAST, K_IS_NULL, K_IS_NOT_NULL, K_NEGATIVE, K_IF, K_LIKE, K_FUNCTION = range(10)
 # qhip_agg_kind
 AGG_SUM, AGG_AVG, AGG_COUNT, AGG_MIN, AGG_MAX = range(5)
 
@@ -149,6 +149,25 @@ class Like(PhysicalExpr):
 
     def __str__(self):
         return f"{self.expr} {'NOT LIKE' if self.negated else 'LIKE'} {self.pattern}"
+
+
+class Function(PhysicalExpr):
+    """physical/expr/function.rs: a built-in function (functions.py) over its argument expressions. The arguments ride in
+    the node's three child slots in order, so more than three cannot be expressed; the arity the function itself needs
+    (EXTRACT: 2) is checked by libqhip with the reference's error text."""
+
+    def __init__(self, func, args: Sequence[PhysicalExpr]):
+        self.func, self.args = func, list(args)
+        if len(self.args) > 3:
+            raise _ffi.InternalError(_ffi.QHIP_INVALID_ARGUMENT, f"{func.name()} requires 2 arguments" if func.name() == "EXTRACT"
+                                     else f"{func.name()}: more than 3 arguments")
+
+    def _lower(self, out):
+        slots = [a._lower(out) for a in self.args] + [-1] * (3 - len(self.args))
+        return out.add(kind=K_FUNCTION, op=self.func.fn_id, left=slots[0], right=slots[1], third=slots[2])
+
+    def __str__(self):
+        return self.func.name()
 
 
 class ExprArray:

@@ -55,6 +55,10 @@ pub const QHIP_EXPR_IS_NOT_NULL: i32 = 5;
 pub const QHIP_EXPR_NEGATIVE: i32 = 6;
 pub const QHIP_EXPR_IF: i32 = 7;
 pub const QHIP_EXPR_LIKE: i32 = 8;
+pub const QHIP_EXPR_FUNCTION: i32 = 9;
+
+// ---------------------------------------------------------------- qhip_function
+pub const QHIP_FN_EXTRACT: i32 = 0;
 
 // ---------------------------------------------------------------- qhip_agg_kind
 pub const QHIP_AGG_SUM: i32 = 0;

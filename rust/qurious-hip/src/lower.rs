@@ -3,7 +3,7 @@
 //! 352-400). The physical expression objects themselves cannot be lowered: `trait PhysicalExpr` (physical/expr/mod.rs:33-35)
 //! has no `as_any`, so the shim starts from the logical plan, where every node is a public enum.
 //!
-//! Anything the backend does not accelerate (`Function`, sub-queries, `Decimal256`, ...) is `HipError::Unsupported`: the
+//! Anything the backend does not accelerate (functions other than `EXTRACT`, sub-queries, `Decimal256`, ...) is `HipError::Unsupported`: the
 //! planner then builds the reference's CPU node for that part of the plan.
 use std::ffi::CString;
 use std::os::raw::c_char;
@@ -14,7 +14,7 @@ use qurious::common::table_schema::FIELD_QUALIFIERS_META_KEY;
 use qurious::datatypes::operator::Operator;
 use qurious::datatypes::scalar::ScalarValue;
 use qurious::error::Error;
-use qurious::logical::expr::{AggregateExpr, AggregateOperator, BinaryExpr, Column, LogicalExpr};
+use qurious::logical::expr::{AggregateExpr, AggregateOperator, BinaryExpr, Column, Function, LogicalExpr};
 
 use crate::ffi::*;
 
@@ -322,6 +322,24 @@ impl ExprArray {
                 n.left = value;
                 n.right = pattern;
                 n.op = like.negated as i32;
+                Ok(self.push(n))
+            }
+            // EXTRACT(part FROM x) = Function(DatetimeExtract, [Literal(Utf8(part)), x]) (planner/sql.rs:1013-1018): the arguments
+            // in the child slots, in order; libqhip checks the arity, the part and the argument type (reference error texts,
+            // or QHIP_UNSUPPORTED for what it does not accelerate). Every other function stays with the CPU node.
+            LogicalExpr::Function(Function { func, args }) if func.name() == "EXTRACT" => {
+                if args.len() > 3 {
+                    return Err(HipError::Failed(Error::InvalidArgumentError("EXTRACT requires 2 arguments".to_string())));
+                }
+                let mut n = blank(QHIP_EXPR_FUNCTION);
+                n.op = QHIP_FN_EXTRACT;
+                let mut slots = [-1i32; 3];
+                for (k, a) in args.iter().enumerate() {
+                    slots[k] = self.lower(a, schema)?;
+                }
+                n.left = slots[0];
+                n.right = slots[1];
+                n.third = slots[2];
                 Ok(self.push(n))
             }
             other => unsupported(format!("expression {other} is not accelerated")),
