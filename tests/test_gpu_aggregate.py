@@ -215,6 +215,45 @@ def test_device_side_output_assembly_matches_host_side(ctx, oracle, monkeypatch)
             assert (a is None and b is None) or abs(a - b) <= 1e-6 * max(1.0, abs(b))
 
 
+def test_device_side_output_assembly_with_uploaded_descriptors(ctx, oracle, monkeypatch):
+    """25 output columns (2 keys + 23 aggregates): more than k_agg_finalize takes as a kernel argument (24), so the column
+    descriptors are uploaded. SUM / COUNT / MIN / MAX / AVG in turn over two Int64 columns and a Decimal128 column with NULLs
+    (AVG always over the Decimal128 column: like the reference, the engine averages only Decimal128 and Float64)."""
+    monkeypatch.setenv("QHIP_AGG_DEVICE_FINALIZE_MIN_GROUPS", "1")
+    monkeypatch.setenv("QHIP_AGG_REPLICAS", "1")
+    rng = np.random.default_rng(23)
+    n = 3000
+    D = decimal.Decimal
+    dec = pa.decimal128(15, 2)
+    schema = pa.schema([pa.field("k1", I64), pa.field("k2", I64), pa.field("a", I64), pa.field("b", I64), pa.field("x", dec)])
+    batch = pa.RecordBatch.from_arrays([
+        pa.array(rng.integers(0, 20, n), type=I64, mask=rng.random(n) < 0.05),
+        pa.array(rng.integers(0, 15, n), type=I64),
+        pa.array(rng.integers(-10**9, 10**9, n), type=I64, mask=rng.random(n) < 0.1),
+        pa.array(rng.integers(-50, 50, n), type=I64, mask=rng.random(n) < 0.3),
+        pa.array([D(int(v)).scaleb(-2) for v in rng.integers(-10**9, 10**9, n)], type=dec, mask=rng.random(n) < 0.1)], schema=schema)
+    scan = table_scan(schema, [batch])
+    args = [(col("a", 2), I64), (col("b", 3), I64), (col("x", 4), dec)]
+    aggs = []
+    for i in range(23):
+        e, t = args[i % 3]
+        kind = i % 5
+        if kind == 0:
+            aggs.append(q.SumAggregateExpr(e, t))
+        elif kind == 1:
+            aggs.append(q.CountAggregateExpr(e))
+        elif kind == 2:
+            aggs.append(q.MinAggregateExpr(e, t))
+        elif kind == 3:
+            aggs.append(q.MaxAggregateExpr(e, t))
+        else:
+            aggs.append(q.AvgAggregateExpr(col("x", 4), dec, q.avg_return_type(dec)))
+    plan = q.HashAggregate(None, scan, [col("k1", 0), col("k2", 1)], aggs)
+    got, want = plan.execute()[0], oracle.execute(plan)[0]
+    assert got.num_columns == 25 and [f.type for f in got.schema] == [f.type for f in want.schema]
+    assert sorted_rows([got]) == sorted_rows([want]) and 250 <= got.num_rows <= 315
+
+
 def test_partitioned_path_for_many_groups(ctx, oracle, monkeypatch):
     """the partitioned aggregate (rows split by key-hash bin, per-bin LDS aggregation, one HBM merge per group — what runs for
     many groups on a big input) forced on: every cell kind, NULL keys and values, two keys incl. Utf8, a fused filter,
