@@ -195,7 +195,8 @@ typedef struct qhip_exec_stats {
                               * buffers of the columns its expressions reference; the offsets of a Utf8 column whose every
                               * value is 1 byte long are not read) — what a roofline figure must be computed from.
                               * Hash join: bytes the probe kernel reads per PROBE row (key + fused-filter columns). */
-  double build_ms;           /* hash join: key evaluation + table build, first launch .. probe kernel (main_kernel_ms is the
+  double build_ms;           /* aggregate through the wide-key stage: the stage's memset + kernel;
+                              * hash join: key evaluation + table build, first launch .. probe kernel (main_kernel_ms is the
                               * probe kernel alone, total_device_ms the whole call incl. pair emission) */
   int64_t build_rows;        /* hash join: rows of the build side */
   double build_bytes_per_row;/* hash join: bytes of build-side columns its key / fused-filter expressions read per row */
@@ -221,6 +222,17 @@ uint64_t qhip_ctx_sync_count(const qhip_ctx* ctx);
  * phases. Every event record is a packet of its own on the stream (~5 us of stream time each; a two-join query recorded
  * ten), so they are OFF by default (the fields then read 0): switch them on for instrumented runs (or QHIP_TIMING=1). */
 int qhip_ctx_set_timing(qhip_ctx* ctx, int32_t on);
+/* Wide group keys. The reference hashes group keys of any length and any number of columns (utils/array.rs:171-210); the
+ * aggregate kernels pack a key into at most 8 words (a Utf8 key: 7 words, 55 bytes) and answer QHIP_UNSUPPORTED beyond.
+ * With the switch on, a grouped aggregate whose key columns are plain columns first replaces the key by one 32-bit group
+ * code per row (exact: keys are compared, not only hashed), aggregates on that code, and gathers the key columns of the
+ * result from one representative input row per group. mode 0: off (the default); 1: when the packed key would not fit;
+ * 2: every grouped aggregate whose keys are plain columns (tests, fuzzing). Up to 32 key columns and 2^30 input rows;
+ * computed key expressions are not encoded. While the mode was never set, the environment's QHIP_AGG_WIDE_KEYS (0/1/2) is
+ * read per call. */
+int qhip_ctx_set_wide_group_keys(qhip_ctx* ctx, int32_t mode);
+/* aggregate calls of this context that went through the wide-key encoding stage so far */
+int64_t qhip_ctx_wide_key_aggregates(qhip_ctx* ctx);
 /* Deferred sizing. A hash join normally waits for its pair total to size its output (one host round trip per join). It
  * also remembers, per join (expressions, join type, probe rows — not the data), how many pairs it produced. While
  * deferred sizes are allowed, an Inner join with such a hint does NOT wait: its output is allocated for the remembered

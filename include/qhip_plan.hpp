@@ -37,6 +37,9 @@ class Context {
   Context& operator=(const Context&) = delete;
   qhip_ctx* raw() const { return ctx_; }
   void check(int rc) const { if (rc != QHIP_OK) throw Error(rc, qhip_last_error(ctx_)); }
+  // GROUP BY keys that do not fit the packed key words are encoded to group codes first (qhip.h: 0 off, 1 when needed, 2 always)
+  void set_wide_group_keys(int mode) const { check(qhip_ctx_set_wide_group_keys(ctx_, mode)); }
+  int64_t wide_key_aggregates() const { return qhip_ctx_wide_key_aggregates(ctx_); }
 
  private:
   qhip_ctx* ctx_ = nullptr;

@@ -134,6 +134,8 @@ def load_library() -> C.CDLL:
             "qhip_ctx_synchronize": (C.c_int, [vp]),
             "qhip_ctx_sync_count": (C.c_uint64, [vp]),
             "qhip_ctx_set_timing": (C.c_int, [vp, i32]),
+            "qhip_ctx_set_wide_group_keys": (C.c_int, [vp, i32]),
+            "qhip_ctx_wide_key_aggregates": (i64, [vp]),
             "qhip_ctx_allow_deferred_sizes": (C.c_int, [vp, i32]),
             "qhip_ctx_forget_plans": (C.c_int, [vp]),
             "qhip_ctx_device_name": (C.c_int, [vp, C.c_char_p, C.c_size_t]),
@@ -232,6 +234,16 @@ class Context:
     def set_timing(self, on: bool):
         """qhip_exec_stats timings (HIP events around an operator's phases) on / off; off by default, they cost stream time."""
         self.check(self.lib.qhip_ctx_set_timing(self.handle, 1 if on else 0))
+
+    def set_wide_group_keys(self, mode: int):
+        """GROUP BY keys wider than the packed 8 key words (long Utf8 values, many columns) are first encoded to one group code
+        per row: 0 off, 1 when the key does not fit, 2 every grouped aggregate over plain key columns. Never set: the
+        environment's QHIP_AGG_WIDE_KEYS decides per call (default 0)."""
+        self.check(self.lib.qhip_ctx_set_wide_group_keys(self.handle, int(mode)))
+
+    def wide_key_aggregates(self) -> int:
+        """Aggregate calls of this context that went through the wide-key encoding stage so far."""
+        return int(self.lib.qhip_ctx_wide_key_aggregates(self.handle))
 
     def sync_count(self) -> int:
         """Host waits on the device made through the library so far (the difference around a plan = its round trips)."""

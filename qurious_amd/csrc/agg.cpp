@@ -6,7 +6,8 @@
 //
 // hash_aggregate (the driver, at the end of the file) is the operator's outline; every stage is a function of this file:
 //    1  validate_agg_args
-//    2  maybe_prepartition      mid-sized input, many groups: rows ordered by key hash into parts, then hash_aggregate again over them
+//    2  maybe_encode_wide_key   a key that does not fit the packed key words: one group code per row, then hash_aggregate again on the code
+//       maybe_prepartition      mid-sized input, many groups: rows ordered by key hash into parts, then hash_aggregate again over them
 //    3  resolve_agg_inputs      deferred columns, Utf8 key lengths, |value| bounds, record copies
 //    4  lookup_or_lower_plan    plan cache, twin-plan learning;  bind_plan_to_input: kernel arguments, sizes, page-locked scratch
 //    5  decide_launch_shape     LDS slots, wide / cons / parts, grid, the first table's size and replicas
@@ -231,6 +232,9 @@ struct AggTuning {
   int parts_max_factor;       // QHIP_AGG_PARTS_MAX_FACTOR: a part of more than this many times the average is sliced (policy)
   bool pinned_slots;          // QHIP_AGG_PINNED_SLOTS=0: the first dense slots come back by copy, not straight from the compaction (measurement)
   bool prof;                  // QHIP_AGG_PROF: print the fused kernel's phase timers (measurement; needs a kernel built with P::PROF)
+  int wide_keys;              // QHIP_AGG_WIDE_KEYS 0 never / 1 when the packed key does not fit / 2 every grouped aggregate over plain key
+                              // columns: keys encoded to group codes first (policy, off; 2 = tests) — the context's own mode goes first
+  int wide_key_hash_bits;     // QHIP_AGG_WIDE_KEY_HASH_BITS (1..63): only so many bits of the encoding's hash (test forcing: long probe chains)
 };
 static AggTuning read_agg_tuning() {
   AggTuning t;
@@ -266,6 +270,8 @@ static AggTuning read_agg_tuning() {
   t.parts_max_factor = env_int("QHIP_AGG_PARTS_MAX_FACTOR", 4);
   t.pinned_slots = env_int("QHIP_AGG_PINNED_SLOTS", 1) != 0;
   t.prof = env_int("QHIP_AGG_PROF", 0) != 0;
+  t.wide_keys = env_int("QHIP_AGG_WIDE_KEYS", 0);
+  t.wide_key_hash_bits = env_int("QHIP_AGG_WIDE_KEY_HASH_BITS", 0);
   return t;
 }
 
@@ -356,7 +362,7 @@ static uint64_t agg_hint_key(const qhip_expr* exprs, int n_exprs, int pred_root,
 
 static qhip_table* hash_aggregate(Ctx* ctx, const qhip_table* in, const qhip_expr* exprs, int n_exprs, int pred_root,
                                   const int32_t* group_roots, int n_groups, const qhip_agg* aggs, int n_aggs,
-                                  const char* const* out_names, const AggParts* parts = nullptr);
+                                  const char* const* out_names, const AggParts* parts = nullptr, bool key_encoded = false);
 
 // ---------------------------------------------------------------- stage 1: validate
 static void validate_agg_args(const qhip_expr* exprs, int n_exprs, int pred_root, const int32_t* group_roots, int n_groups,
@@ -366,6 +372,142 @@ static void validate_agg_args(const qhip_expr* exprs, int n_exprs, int pred_root
   for (int k = 0; k < n_groups; ++k)
     if (group_roots[k] < 0 || group_roots[k] >= n_exprs) fail(QHIP_INVALID_ARGUMENT, "group expression index out of range");
   if (pred_root >= n_exprs) fail(QHIP_INVALID_ARGUMENT, "predicate index out of range");
+}
+
+// ---------------------------------------------------------------- stage 2: wide group keys
+// The reference hashes group keys of any length and any number of columns (utils/array.rs:171-210); a packed key has 8 words (a
+// Utf8 key 7 of them). A key that does not fit never reaches the aggregate: k_widekey_encode (device/qhip_widekey.inc) gives every
+// row the number of ONE row with the same key — exact, the keys themselves are compared — and hash_aggregate runs again, with
+// all its paths, over a view of the input whose one group key is that Int32 column. The result's code column is then the index
+// vector through which the key columns are gathered from the input (deferred, validity included). 16 bytes of HBM per input row
+// (the slot table, twice the rows) + 4 for the codes while the stage runs. Rows the scan predicate drops are encoded for nothing.
+// mode 1: when the packed key does not fit; 2: every grouped aggregate whose keys are plain columns (tests, fuzzing).
+// Returns the result, or nullptr when the input is aggregated as it is.
+static bool plain_column_keys(const qhip_table* in, const qhip_expr* exprs, const int32_t* group_roots, int n_groups) {
+  for (int k = 0; k < n_groups; ++k) {
+    const qhip_expr& e = exprs[group_roots[k]];
+    if (e.kind != QHIP_EXPR_COLUMN || e.column < 0 || e.column >= (int)in->cols.size()) return false;
+  }
+  return true;
+}
+static qhip_table* maybe_encode_wide_key(Ctx* ctx, const AggTuning& tune, int mode, const qhip_table* in, const qhip_expr* exprs, int n_exprs,
+                                         int pred_root, const int32_t* group_roots, int n_groups, const qhip_agg* aggs, int n_aggs,
+                                         const char* const* out_names) {
+  if (mode <= 0 || n_groups <= 0 || !plain_column_keys(in, exprs, group_roots, n_groups)) return nullptr;
+  std::vector<int32_t> key_cols((size_t)n_groups);
+  for (int k = 0; k < n_groups; ++k) key_cols[(size_t)k] = exprs[group_roots[k]].column;
+  for (int32_t col : key_cols) check_key_type(in->cols[(size_t)col].type);
+  if (mode == 1) {   // (what resolve_agg_inputs is about to do anyway: nothing is gathered or measured twice)
+    resolve_referenced(ctx, in, exprs, n_exprs, true);
+    std::vector<InputCol> icols = input_cols_of(in, true);
+    ensure_utf8_key_lengths(ctx, in, exprs, n_exprs, group_roots, n_groups, icols);
+    if (packed_key_fits(icols, key_cols.data(), n_groups)) return nullptr;
+  }
+  if (n_groups > kWideKeyCols) fail(QHIP_UNSUPPORTED, "group key of more than 32 columns is not accelerated");
+  // 1. an exact row count, the key columns materialised
+  const bool deferred_size = in->rows_dev != nullptr;
+  settle_rows(in);
+  const int64_t N = in->num_rows;
+  if (N > ((int64_t)1 << 30)) fail(QHIP_UNSUPPORTED, "wide group key over more than 2^30 input rows is not accelerated");
+  // (a join of deferred size that produced nothing has no output batches, hash_join.rs:363-372)
+  const bool zero_batches = in->no_batches() || (deferred_size && N == 0);
+  WideKeyCols wk;
+  memset(&wk, 0, sizeof wk);
+  std::vector<DevColumn> keys;
+  for (int k = 0; k < n_groups; ++k) {
+    const DevColumn& c = resolved(ctx, in->cols[(size_t)key_cols[(size_t)k]]);
+    WideKeyCol& d = wk.c[k];
+    d.v = c.values ? c.values->ptr : nullptr;
+    d.d = c.data ? c.data->as<uint8_t>() : nullptr;
+    d.n = c.validity ? c.validity->as<uint8_t>() : nullptr;
+    d.width = (uint32_t)dtype_width(c.type);   // (0: Utf8 — check_key_type has let nothing else without a width through)
+    keys.push_back(c);
+  }
+  // 2. the codes
+  auto code = std::make_shared<DevBuf>((size_t)N * 4);
+  const uint32_t nslots = std::max<uint32_t>(1024, pow2_ceil((uint64_t)std::max<int64_t>(N, 1) * 2));
+  DevBuf table((size_t)nslots * 8);
+  struct Events {   // (timings asked for: a pair of the stage's own — the aggregate behind it records the context's)
+    hipEvent_t e[2] = {nullptr, nullptr};
+    ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
+    hipEvent_t operator[](int k) const { return e[k]; }
+  } ev;
+  if (ctx->timing) for (hipEvent_t& e : ev.e) { QHIP_HIP_CHECK(hipEventCreate(&e)); }
+  if (N > 0) {
+    if (ev[0]) (void)hipEventRecord(ev[0], ctx->stream);
+    QHIP_HIP_CHECK(hipMemsetAsync(table.ptr, 0, (size_t)nslots * 8, ctx->stream));
+    const int bits = tune.wide_key_hash_bits;
+    launch_widekey_encode(wk, n_groups, table.as<uint64_t>(), nslots, bits > 0 && bits < 64 ? (1ULL << bits) - 1 : ~0ULL, code->as<int32_t>(), (uint64_t)N, ctx->stream);
+    if (ev[1]) (void)hipEventRecord(ev[1], ctx->stream);
+  }
+  // 3. the input's columns + the code column; 4. the one group key is that column
+  qhip_table view;
+  view.ctx = ctx;
+  view.names = in->names;
+  view.nullable = in->nullable;
+  view.cols = in->cols;
+  view.num_rows = N;
+  view.batch_offsets.assign(1, 0);
+  if (!zero_batches) view.batch_offsets.push_back(N);
+  DevColumn cc;
+  cc.type = DType(QHIP_INT32); cc.length = N; cc.values = code;
+  view.names.push_back("group_code");
+  view.nullable.push_back(false);
+  view.cols.push_back(std::move(cc));
+  std::vector<qhip_expr> ex(exprs, exprs + n_exprs);
+  qhip_expr ce;
+  memset(&ce, 0, sizeof ce);
+  ce.kind = QHIP_EXPR_COLUMN; ce.column = (int32_t)in->cols.size(); ce.left = ce.right = ce.third = -1;
+  ex.push_back(ce);
+  const int32_t code_root = n_exprs;
+  // The key columns' own nodes stay in the array. Whatever the predicate and the aggregates do not reach must not count as a
+  // reference any more — every operator below gathers or uploads the columns its expression array names, and a pre-partitioned
+  // input would gather the wide Utf8 keys through its selection vector — so those Column nodes now name the code column.
+  {
+    std::vector<char> reached((size_t)n_exprs, 0);
+    std::vector<int32_t> todo;
+    if (pred_root >= 0) todo.push_back(pred_root);
+    for (int k = 0; k < n_aggs; ++k) todo.push_back(aggs[k].expr);
+    while (!todo.empty()) {
+      const int32_t k = todo.back();
+      todo.pop_back();
+      if (k < 0 || k >= n_exprs || reached[(size_t)k]) continue;
+      reached[(size_t)k] = 1;
+      todo.push_back(ex[(size_t)k].left); todo.push_back(ex[(size_t)k].right); todo.push_back(ex[(size_t)k].third);
+    }
+    for (int k = 0; k < n_exprs; ++k)
+      if (!reached[(size_t)k] && ex[(size_t)k].kind == QHIP_EXPR_COLUMN) ex[(size_t)k].column = ce.column;
+  }
+  std::vector<std::string> names;
+  for (int k = 0; k < n_groups + n_aggs; ++k) names.push_back(out_names && out_names[k] ? out_names[k] : ("col" + std::to_string(k)));
+  std::vector<const char*> inner_names{"group_code"};
+  for (int k = 0; k < n_aggs; ++k) inner_names.push_back(names[(size_t)(n_groups + k)].c_str());
+  // 5. the aggregate itself, unchanged (scan predicate and aggregate list as they came)
+  std::unique_ptr<qhip_table> res(hash_aggregate(ctx, &view, ex.data(), n_exprs + 1, pred_root, &code_root, 1, aggs, n_aggs, inner_names.data(), nullptr, true));
+  ++ctx->wide_key_aggregates;
+  if (ev[0] && N > 0) {   // the stage's memset + kernel, in the statistics' build_ms
+    float ms = 0;
+    if (sync_event(ev[1]) == hipSuccess && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) ctx->stats.build_ms = ms;
+  }
+  // 6. [code, aggregates ...] -> [the key columns at the representative rows, aggregates ...]
+  const int64_t G = res->num_rows;
+  std::unique_ptr<qhip_table> out(new qhip_table());
+  out->ctx = ctx;
+  out->names = names;
+  out->nullable.assign(names.size(), true);
+  out->num_rows = G;
+  out->batch_offsets = res->offsets();
+  if (G > 0) {
+    const DevColumn& rc = resolved(ctx, res->cols[0]);   // (few groups: assembled on the host, uploaded here)
+    defer_gather(ctx, keys, rc.values, (uint64_t)G, false, out->cols);
+  } else {
+    std::vector<HostColumn> hk((size_t)n_groups);
+    for (int k = 0; k < n_groups; ++k) hk[(size_t)k].init_fixed(keys[(size_t)k].type, 0);
+    std::unique_ptr<qhip_table> empty(table_from_host(ctx, std::vector<std::string>(names.begin(), names.begin() + n_groups), std::vector<bool>((size_t)n_groups, true), hk, 0, true));
+    for (auto& c : empty->cols) out->cols.push_back(std::move(c));
+  }
+  for (size_t k = 1; k < res->cols.size(); ++k) out->cols.push_back(std::move(res->cols[k]));
+  return out.release();
 }
 
 // ---------------------------------------------------------------- stage 2: pre-partitioning
@@ -1133,7 +1275,7 @@ static qhip_table* collect_slots(const AggCall& c, AggRun& r, uint32_t& G, std::
 // ---------------------------------------------------------------- the driver
 static qhip_table* hash_aggregate(Ctx* ctx, const qhip_table* in, const qhip_expr* exprs, int n_exprs, int pred_root,
                                   const int32_t* group_roots, int n_groups, const qhip_agg* aggs, int n_aggs,
-                                  const char* const* out_names, const AggParts* parts) {
+                                  const char* const* out_names, const AggParts* parts, bool key_encoded) {
   AggCall c;
   c.tune = read_agg_tuning();
   c.t_begin = std::chrono::steady_clock::now();
@@ -1145,11 +1287,21 @@ static qhip_table* hash_aggregate(Ctx* ctx, const qhip_table* in, const qhip_exp
   ctx->stats_timing_pending = 0;
 
   c.hint_key = parts ? parts->hint_key : agg_hint_key(exprs, n_exprs, pred_root, group_roots, n_groups, aggs, n_aggs);
+  const int wide_mode = key_encoded || parts ? 0 : ctx->wide_keys_mode >= 0 ? ctx->wide_keys_mode : c.tune.wide_keys;
+  if (wide_mode)
+    if (qhip_table* t = maybe_encode_wide_key(ctx, c.tune, wide_mode, in, exprs, n_exprs, pred_root, group_roots, n_groups, aggs, n_aggs, out_names)) return t;
   if (!parts)
     if (qhip_table* t = maybe_prepartition(ctx, c.tune, c.hint_key, in, exprs, n_exprs, pred_root, group_roots, n_groups, aggs, n_aggs, out_names)) return t;
 
   const std::vector<InputCol> icols = resolve_agg_inputs(ctx, c.tune, in, exprs, n_exprs, group_roots, n_groups);
-  c.plan_ptr = lookup_or_lower_plan(ctx, c.tune, in, icols, exprs, n_exprs, pred_root, group_roots, n_groups, aggs, n_aggs);
+  try {
+    c.plan_ptr = lookup_or_lower_plan(ctx, c.tune, in, icols, exprs, n_exprs, pred_root, group_roots, n_groups, aggs, n_aggs);
+  } catch (const Error& e) {
+    // wide keys are on, yet the key that does not fit is computed: the encoding stage takes plain key columns only
+    if (wide_mode == 1 && e.code == QHIP_UNSUPPORTED && !plain_column_keys(in, exprs, group_roots, n_groups))
+      fail(QHIP_UNSUPPORTED, std::string(e.what()) + " (wide group keys: computed key expressions are not encoded)");
+    throw;
+  }
   c.mark("planned");
 
   for (int k = 0; k < n_groups + n_aggs; ++k) {

@@ -513,7 +513,7 @@ void ExprGen::emit(int k, std::string& out) {
 // Time32 / Time64, Decimal128 and Decimal256 and raises an InternalError for anything else. The HIP path takes the same list
 // MINUS Decimal256 (out of scope, DESIGN §8: no such type id crosses the C ABI): a plan with such a key gets the reference's
 // own error text here and the shim keeps the CPU node — a documented gap, not a drop-in.
-static void check_key_type(const DType& t) {
+void check_key_type(const DType& t) {
   switch (t.id) {
     case QHIP_INT64: case QHIP_UINT8: case QHIP_INT32: case QHIP_UTF8: case QHIP_DATE32: case QHIP_DATE64: case QHIP_DECIMAL128:
     case QHIP_TIME32_S: case QHIP_TIME32_MS: case QHIP_TIME64_US: case QHIP_TIME64_NS:
@@ -523,16 +523,34 @@ static void check_key_type(const DType& t) {
   }
 }
 
+int packed_key_words(const DType& t, int utf8_max_len) {
+  if (t.id == QHIP_UTF8) return std::max(1, (utf8_max_len + 1 + 7) / 8);
+  return t.id == QHIP_DECIMAL128 ? 2 : 1;
+}
+
 // words of a packed Utf8 key: the bytes little-endian across the words, the length in the top byte of the last word
 static int utf8_key_words(const ExprSet& es, const std::vector<InputCol>& input, int root) {
   const ENode& nd = es.at(root);
   int maxlen = 7;
   if (nd.kind == QHIP_EXPR_COLUMN && input[(size_t)nd.column].utf8_max_len >= 0) maxlen = input[(size_t)nd.column].utf8_max_len;
   else if (nd.kind == QHIP_EXPR_LITERAL) maxlen = (int)nd.s.size();
-  const int words = std::max(1, (maxlen + 1 + 7) / 8);
+  const int words = packed_key_words(nd.type, maxlen);
   // (up to 7 words = 55 bytes + the length byte per Utf8 key — round 4; rounds 1-3: 4 words — inside the 8 words a whole key may have)
-  if (words > 7) fail(QHIP_UNSUPPORTED, "Utf8 group/join key longer than 55 bytes is not accelerated");
+  if (words > kMaxUtf8KeyWords) fail(QHIP_UNSUPPORTED, "Utf8 group/join key longer than 55 bytes is not accelerated");
   return words;
+}
+
+bool packed_key_fits(const std::vector<InputCol>& input, const int32_t* cols, int n) {
+  int W = 0;
+  bool mask_word = false;
+  for (int k = 0; k < n; ++k) {
+    const InputCol& ic = input[(size_t)cols[k]];
+    mask_word = mask_word || ic.has_nulls || ic.type.id == QHIP_NULL;
+    const int words = packed_key_words(ic.type, ic.utf8_max_len >= 0 ? ic.utf8_max_len : 7);
+    if (ic.type.id == QHIP_UTF8 && words > kMaxUtf8KeyWords) return false;
+    W += words;
+  }
+  return W + (mask_word ? 1 : 0) <= kMaxKeyWords;
 }
 
 static void layout_keys(const ExprSet& es, const std::vector<InputCol>& input, const int32_t* roots, int n, bool with_null_mask,
@@ -547,7 +565,7 @@ static void layout_keys(const ExprSet& es, const std::vector<InputCol>& input, c
     check_key_type(nd.type);
     KeyDesc kd;
     kd.root = roots[k]; kd.type = nd.type; kd.nullable = nd.nullable; kd.word_off = off;
-    kd.words = nd.type.id == QHIP_DECIMAL128 ? 2 : nd.type.id == QHIP_UTF8 ? utf8_key_words(es, input, roots[k]) : 1;
+    kd.words = nd.type.id == QHIP_UTF8 ? utf8_key_words(es, input, roots[k]) : packed_key_words(nd.type, 0);
     off += kd.words;
     keys.push_back(kd);
   }
@@ -616,7 +634,7 @@ void plan_aggregate(const ExprSet& es, const std::vector<InputCol>& input, int p
   if (predicate_root >= 0 && es.at(predicate_root).type.id != QHIP_BOOL)
     fail(QHIP_INVALID_ARGUMENT, "filter predicate must be Boolean, got " + dtype_name(es.at(predicate_root).type));
   layout_keys(es, input, group_roots, n_groups, true, P.keys, P.W, P.null_mask_word);
-  if (P.W > 8) fail(QHIP_UNSUPPORTED, "group key wider than 8 words");
+  if (P.W > kMaxKeyWords) fail(QHIP_UNSUPPORTED, "group key wider than 8 words");
 
   // cells: cell 0 counts the rows of the group
   auto add_cell = [&](int kind, int arg, bool is_min, int words) {

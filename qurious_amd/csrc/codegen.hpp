@@ -59,6 +59,15 @@ class ExprGen {
   std::map<int, int> utf8_key_words_;
 };
 
+// ---------------------------------------------------------------- packed keys
+// Words of one key in a packed key (layout_keys): Decimal128 two, Utf8 by its longest value plus the length byte, else one. A
+// Utf8 key may take kMaxUtf8KeyWords, a whole key (with its null-mask word) kMaxKeyWords; agg.cpp's wide-key stage asks with the
+// same arithmetic whether a key fits.
+constexpr int kMaxUtf8KeyWords = 7, kMaxKeyWords = 8;
+int packed_key_words(const DType& t, int utf8_max_len);
+bool packed_key_fits(const std::vector<InputCol>& input, const int32_t* cols, int n);   // the plain key columns `cols` of `input` as ONE aggregate key
+void check_key_type(const DType& t);   // the reference's hasher types (utils/array.rs:190-210), its error text otherwise
+
 // ---------------------------------------------------------------- aggregate plan
 enum CellKind { CELL_ROWS = 0, CELL_SUM_I128, CELL_SUM_U64, CELL_SUM_F64, CELL_CNT, CELL_MAXORD64, CELL_MAXORD128 };
 

@@ -272,6 +272,10 @@ struct Ctx {
   // of its table slots: decide whether a mid-sized input is ordered by key hash first (agg.cpp, AggParts)
   std::unordered_map<uint64_t, uint32_t> agg_group_hints;
   std::unordered_map<uint64_t, int> agg_slot_words;
+  // wide group keys (agg.cpp maybe_encode_wide_key): qhip_ctx_set_wide_group_keys' mode, -1 = never set (QHIP_AGG_WIDE_KEYS
+  // decides per call); the aggregate calls that went through the stage
+  int wide_keys_mode = -1;
+  int64_t wide_key_aggregates = 0;
   // (total_out: the output table's own host word — the page-locked slot is part of a ring and is reused by later joins, so
   // the verified total is copied where the table can still find it however long it stays unsettled)
   struct PendingSize { uint32_t* slot; uint64_t key; uint64_t capacity; uint64_t dup_hint; std::shared_ptr<uint64_t> total_out; };

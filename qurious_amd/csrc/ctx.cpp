@@ -397,6 +397,14 @@ int qhip_ctx_set_timing(qhip_ctx* ctx, int32_t on) {
   return QHIP_OK;
 }
 
+int qhip_ctx_set_wide_group_keys(qhip_ctx* ctx, int32_t mode) {
+  if (!ctx || mode < 0 || mode > 2) return QHIP_INVALID_ARGUMENT;
+  ctx->wide_keys_mode = mode;
+  return QHIP_OK;
+}
+
+int64_t qhip_ctx_wide_key_aggregates(qhip_ctx* ctx) { return ctx ? ctx->wide_key_aggregates : 0; }
+
 int qhip_ctx_allow_deferred_sizes(qhip_ctx* ctx, int32_t delta) {
   if (!ctx) return QHIP_INVALID_ARGUMENT;
   if (delta == 0) { ctx->allow_deferred_sizes = 0; ctx->pending_sizes.clear(); }   // reset (after an error above a deferred join)

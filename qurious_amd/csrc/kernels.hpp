@@ -129,4 +129,11 @@ void launch_agg_finalize(const uint64_t* dense, uint32_t G_cap, const uint32_t* 
                          const FinCol* cols_dev, int ncols, uint32_t* null_counts, uint32_t* status, hipStream_t s);
 void launch_agg_utf8_key_bytes(const uint64_t* dense, uint32_t G, int slot_words, int src_word, const uint32_t* offsets, uint8_t* data,
                                hipStream_t s);
+// ---- wide group keys -> one 32-bit group code per row (kernels_rel.hip k_widekey_encode, device/qhip_widekey.inc)
+struct WideKeyCol { const void* v; const uint8_t* d; const uint8_t* n; uint32_t width; uint32_t pad; };   // = qh_wk_col; width 0 = Utf8
+constexpr int kWideKeyCols = 32;
+struct WideKeyCols { WideKeyCol c[kWideKeyCols]; };
+// table: nslots (a power of two >= 2 * nrows) zeroed 8-byte slots; code[row] = the representative row of the row's key
+void launch_widekey_encode(const WideKeyCols& cols, int ncols, uint64_t* table, uint32_t nslots, uint64_t hash_mask, int32_t* code, uint64_t nrows,
+                           hipStream_t s);
 }  // namespace qhip

@@ -9,6 +9,7 @@
 
 #include "device/qhip_status.h"
 #include "device/qhip_device.hpp"
+#include "device/qhip_widekey.inc"
 #include "common.hpp"
 #include "kernels.hpp"
 
@@ -1389,6 +1390,36 @@ void launch_agg_utf8_key_bytes(const uint64_t* dense, uint32_t G, int slot_words
   if (!G) return;
   hipLaunchKernelGGL(k_agg_utf8_key_bytes, dim3(grid_for(G)), dim3(QH_BLOCK), 0, s, (const u64*)dense, G, slot_words, src_word,
                      (const u32*)offsets, (u8*)data);
+}
+
+// ================================================================ wide group keys -> group codes
+// GROUP BY keys of any width (the reference hashes any number of columns of any length, utils/array.rs:171-210): every row gets
+// the number of one representative row of its key (device/qhip_widekey.inc: the slot protocol), and the aggregate kernels then
+// group by that one word. The slots are shared by all workgroups, so every access to them is an 8-byte agent-scope atomic;
+// the load in front of the compare-and-swap keeps the rows of an already known key off the atomic path (one CAS per key
+// and contender, not per row). The column descriptors travel as a kernel argument (uniform, scalar loads).
+struct WkSlotHbm {
+  static __device__ __forceinline__ u64 load(const u64* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+  static __device__ __forceinline__ u64 cas(u64* p, u64 desired) {
+    u64 expect = 0;
+    (void)__hip_atomic_compare_exchange_strong(p, &expect, desired, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return expect;   // (0: the slot was empty and is now ours; else the winner's word)
+  }
+};
+struct WideKeyColsArg { qh_wk_col c[QH_WK_MAX_COLS]; };
+static_assert(sizeof(WideKeyCol) == sizeof(qh_wk_col) && kWideKeyCols == QH_WK_MAX_COLS, "host and device descriptors of a wide-key column differ");
+__global__ __launch_bounds__(QH_BLOCK) void k_widekey_encode(WideKeyColsArg cols, int ncols, u64* table, u32 slot_mask, u64 hash_mask, u32* code, u64 nrows) {
+  const u64 stride = (u64)gridDim.x * QH_BLOCK;
+  for (u64 row = (u64)blockIdx.x * QH_BLOCK + threadIdx.x; row < nrows; row += stride)
+    code[row] = qh_wk_insert<WkSlotHbm>(cols.c, ncols, table, slot_mask, hash_mask, (u32)row);
+}
+void launch_widekey_encode(const WideKeyCols& cols, int ncols, uint64_t* table, uint32_t nslots, uint64_t hash_mask, int32_t* code, uint64_t nrows,
+                           hipStream_t s) {
+  if (!nrows) return;
+  WideKeyColsArg a;
+  memcpy(&a, &cols, sizeof a);
+  hipLaunchKernelGGL(k_widekey_encode, dim3(grid_for(nrows, QH_BLOCK, 8192)), dim3(QH_BLOCK), 0, s, a, ncols, (u64*)table, nslots - 1u, (u64)hash_mask, (u32*)code,
+                     (u64)nrows);
 }
 
 // stable sort of (key, value) pairs on the low `bits` bits of the key (rocPRIM LSD radix sort): groups build rows by

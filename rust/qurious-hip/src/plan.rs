@@ -68,6 +68,9 @@ impl HipContext {
             let msg = unsafe { CStr::from_ptr(qhip_last_error(std::ptr::null())) }.to_string_lossy().into_owned();
             return Err(Error::InternalError(msg));
         }
+        // GROUP BY keys of any width, as the reference hashes them (utils/array.rs:171-210): keys that do not fit the packed
+        // key words are encoded to group codes first instead of sending the aggregate back to the CPU node
+        unsafe { qhip_ctx_set_wide_group_keys(raw, 1) };
         Ok(Arc::new(Self { raw, lock: Mutex::new(()), tables: Mutex::new(HashMap::new()) }))
     }
     pub fn raw(&self) -> *mut qhip_ctx {
