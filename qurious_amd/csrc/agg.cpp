@@ -170,31 +170,10 @@ void check_status_words(const uint32_t* st) {
   if (st[QS_ARITH_OVERFLOW]) fail(QHIP_EXEC_ERROR, "Arrow error: Arithmetic overflow: Overflow happened on integer division");
 }
 
-static uint32_t pow2_ceil(uint64_t x) {
-  uint64_t p = 1;
-  while (p < x) p <<= 1;
-  return (uint32_t)std::min<uint64_t>(p, 1ULL << 31);
-}
-
 // ---------------------------------------------------------------- the operator's state
 // The input of a mid-sized many-group aggregate, ordered by key hash into one part per workgroup (qk_filter_agg_parts reads part
 // p = rows [runs[p * stride], runs[(p + 1) * stride]) of the view and appends its groups to the dense slots: AggLaunch)
 struct AggParts { const uint32_t* runs; uint32_t stride; int n_parts; uint64_t hint_key; };
-
-// a switch whose default depends on what the call finds out later (the launch shape)
-struct EnvInt {
-  bool set = false;     // in the environment at all, even as an empty string
-  bool given = false;   // set to a non-empty value
-  int value = 0;
-  int or_default(int dflt) const { return given ? value : dflt; }
-};
-static EnvInt env_opt(const char* name) {
-  const char* v = getenv(name);
-  EnvInt e;
-  e.set = v != nullptr;
-  if (v && *v) { e.given = true; e.value = atoi(v); }
-  return e;
-}
 
 // Every environment switch of the aggregate, read ONCE at the top of a hash_aggregate call (per call, the recursive one over the
 // parts included: tests flip them between executions of one process). Nothing below read_agg_tuning looks at the environment.
@@ -425,7 +404,7 @@ static qhip_table* maybe_encode_wide_key(Ctx* ctx, const AggTuning& tune, int mo
   }
   // 2. the codes
   auto code = std::make_shared<DevBuf>((size_t)N * 4);
-  const uint32_t nslots = std::max<uint32_t>(1024, pow2_ceil((uint64_t)std::max<int64_t>(N, 1) * 2));
+  const uint32_t nslots = std::max<uint32_t>(1024, pow2_ceil32((uint64_t)std::max<int64_t>(N, 1) * 2));
   DevBuf table((size_t)nslots * 8);
   struct Events {   // (timings asked for: a pair of the stage's own — the aggregate behind it records the context's)
     hipEvent_t e[2] = {nullptr, nullptr};
@@ -732,7 +711,7 @@ static void decide_launch_shape(const AggCall& c, AggRun& r) {
   // otherwise all merge into the same handful of slots at the end of the kernel (measured: ~45 us of a 470 us kernel).
   // The host merges the replicas (<= 32 x G slots). More groups than the small table holds -> the kernel bails out
   // early on the overflow flag -> one un-replicated table sized for the row count, x16 until it fits.
-  const uint32_t cap_max = r.cap_max = plan.W == 0 ? 1 : std::max<uint32_t>(1024, pow2_ceil((uint64_t)std::max<int64_t>(N, 1) * 2));
+  const uint32_t cap_max = r.cap_max = plan.W == 0 ? 1 : std::max<uint32_t>(1024, pow2_ceil32((uint64_t)std::max<int64_t>(N, 1) * 2));
   r.cap = plan.W == 0 ? 1 : std::min<uint32_t>(cap_max, (uint32_t)tune.initial_slots);
   r.replicas = plan.W == 0 ? 1 : (uint32_t)tune.replicas;
   if (plan.W > 0 && tune.partition_mode == 2) {   // tests: the partitioned path on every grouped aggregate
@@ -741,15 +720,15 @@ static void decide_launch_shape(const AggCall& c, AggRun& r) {
   }
   if (c.parts) {   // the HBM table only takes what an LDS table cannot hold (a part with more groups than planned)
     r.replicas = 1;
-    r.cap = std::min<uint32_t>(cap_max, std::max<uint32_t>(1u << 16, pow2_ceil((uint64_t)plan.last_groups / 2 + 1)));   // (+ the sliced parts' groups; grown x16 on overflow like any table)
+    r.cap = std::min<uint32_t>(cap_max, std::max<uint32_t>(1u << 16, pow2_ceil32((uint64_t)plan.last_groups / 2 + 1)));   // (+ the sliced parts' groups; grown x16 on overflow like any table)
   } else if (plan.W > 0 && plan.last_groups > r.cap / 4) {
     // the same plan produced many groups last time: go straight to one table with room for them
-    r.cap = std::min<uint32_t>(cap_max, std::max<uint32_t>(1u << 16, pow2_ceil((uint64_t)plan.last_groups * 2)));
+    r.cap = std::min<uint32_t>(cap_max, std::max<uint32_t>(1u << 16, pow2_ceil32((uint64_t)plan.last_groups * 2)));
     r.replicas = 1;
   } else if (plan.W > 0 && plan.last_groups > 0 && plan.last_groups * 16 < r.cap) {
     // ... or very few (Q1: 4): 16 slots per expected group are plenty, and clearing + compacting the replicated table
     // (both proportional to its size, both on the critical path of the call) shrink with it
-    r.cap = std::min<uint32_t>(r.cap, std::max<uint32_t>(64, pow2_ceil((uint64_t)plan.last_groups * 16)));
+    r.cap = std::min<uint32_t>(r.cap, std::max<uint32_t>(64, pow2_ceil32((uint64_t)plan.last_groups * 16)));
   }
 }
 
@@ -952,7 +931,7 @@ static bool launch_partitioned(const AggCall& c, const AggRun& r, const HAggLaun
   const uint32_t per_bin = std::max<uint32_t>(16, l_nslots_p * (l_nslots_p > r.l_nslots ? 5 : 3) / 8);   // groups a bin should hold
   uint32_t n_bins = 16;
   while (n_bins < 4096 && (uint64_t)n_bins * per_bin < std::max<uint32_t>(plan.last_groups, 1)) n_bins *= 2;
-  if (tune.part_bins >= 16) n_bins = (uint32_t)pow2_ceil((uint64_t)std::min(4096, tune.part_bins));
+  if (tune.part_bins >= 16) n_bins = (uint32_t)pow2_ceil32((uint64_t)std::min(4096, tune.part_bins));
   uint64_t g1 = std::max<uint64_t>(1, std::min<uint64_t>(((uint64_t)N + 255) / 256, (uint64_t)ctx->num_cus * (uint64_t)tune.part_wgs_per_cu));
   const uint64_t rows_per_wg = ((((uint64_t)N + g1 - 1) / g1) + 255) / 256 * 256;
   g1 = ((uint64_t)N + rows_per_wg - 1) / rows_per_wg;

@@ -332,5 +332,26 @@ inline int env_int(const char* name, int dflt) {
   const char* v = getenv(name);
   return (v && *v) ? atoi(v) : dflt;
 }
+// a switch whose default depends on what the call finds out later (the launch shape)
+struct EnvInt {
+  bool set = false;     // in the environment at all, even as an empty string
+  bool given = false;   // set to a non-empty value
+  int value = 0;
+  int or_default(int dflt) const { return given ? value : dflt; }
+};
+inline EnvInt env_opt(const char* name) {
+  const char* v = getenv(name);
+  EnvInt e;
+  e.set = v != nullptr;
+  if (v && *v) { e.given = true; e.value = atoi(v); }
+  return e;
+}
+// the smallest power of two >= x, at most 2^31; the smallest b with 2^b >= x
+inline uint32_t pow2_ceil32(uint64_t x) {
+  uint64_t p = 1;
+  while (p < x) p <<= 1;
+  return (uint32_t)(p < (1ULL << 31) ? p : (1ULL << 31));
+}
+inline int log2u(uint32_t x) { int b = 0; while ((1u << b) < x) ++b; return b; }
 
 }  // namespace qhip

@@ -19,8 +19,6 @@ using namespace qhip;
 
 namespace {
 
-int log2u(uint32_t x) { int b = 0; while ((1u << b) < x) ++b; return b; }
-
 void partition_by_key(Ctx* ctx, const qhip_table* in, const qhip_expr* exprs, int n_exprs, const int32_t* roots, int n_keys, int n_parts,
                       qhip_table** out_parts) {
   QHIP_HIP_CHECK(hipSetDevice(ctx->device));

@@ -11,6 +11,7 @@ import pytest
 
 import qurious_amd as q
 from qurious_amd import JoinType, Operator, queries, synth
+from qurious_amd.exchange import sorted_build_counts
 
 from .helpers import col, lit_i64, rows_of
 
@@ -173,3 +174,45 @@ def test_join_with_a_build_side_tail_over_a_join_of_deferred_size(ctx, oracle, j
         agg = q.HashAggregate(pa.schema([pa.field("g", I64), pa.field("n", I64), pa.field("s", I64)]), outer, [g],
                               [q.CountAggregateExpr(q.Literal(q.ScalarValue.Int64(1))), q.SumAggregateExpr(v, I64)])
         assert sorted(rows_of(agg.execute()), key=str) == sorted(rows_of(oracle.execute(agg)), key=str), (execution, join_type)
+
+
+def test_several_repeats_within_one_join_over_a_build_side_of_deferred_size(ctx, oracle, monkeypatch):
+    """One execution of a Left join that has to start over three times: its build side is an Inner join of deferred size
+    (made exact first: a build-side tail), the build key arrives out of order under the forced sorted dense build (the atomic
+    build takes over), one build key is there twice (the speculation on unique keys fails) — the fourth attempt builds the CSR.
+    The second execution knows all of it from the hints and waits for the device less often."""
+    monkeypatch.setenv("QHIP_JOIN_DENSE", "2")
+    monkeypatch.setenv("QHIP_JOIN_DENSE_SORTED", "2")
+    # the outer join's build key stays a gather of the probe table's column, whose value range is that column's. As a materialised
+    # key column of a join of deferred size its range is reduced over the capacity, pad rows included: what the pool's memory
+    # held there decides whether the dense layout still applies, and with it whether the sorted build is tried at all.
+    monkeypatch.setenv("QHIP_JOIN_KEY_MATERIALIZE", "0")
+    rng = np.random.default_rng(12)
+    nb, npr, n3 = 3100, 4700, 5300
+    # ascending build keys: the inner join's own sorted build stays in order
+    build = _table(["bk", "bv"], [pa.array(np.arange(nb), I64), pa.array(rng.integers(0, 100, nb), I64)])
+    pk = rng.permutation(npr)              # distinct, out of order; the rows with pk < nb match: the inner join's output
+    hits = np.flatnonzero(pk < nb)
+    pk[hits[7]] = pk[hits[3]]              # ... with ONE key twice
+    probe = _table(["pk", "pv"], [pa.array(pk, I64), pa.array(rng.integers(0, 23, npr), I64)], 1024)
+    third = _table(["k3", "w"], [pa.array(rng.integers(0, nb * 2, n3), I64, mask=rng.random(n3) < 0.05), pa.array(rng.integers(0, 5, n3), I64)], 2048)
+    (bs, bt), (ps, pt) = build, probe
+
+    def plans():
+        inner = q.HashJoinExec.try_new(q.Scan(bs, bt), q.Scan(ps, pt), JoinType.Inner, [(col("bk", 0), col("pk", 0))], None)
+        return inner, q.HashJoinExec.try_new(inner, q.Scan(*third), JoinType.Left, [(col("pk", 2), col("k3", 0))], None)
+
+    inner, outer = plans()
+    assert inner.execute_device().num_rows == nb   # alone: waits for its size and remembers it, so that it is deferred below
+    want = oracle.execute(outer)
+    _, fb0 = sorted_build_counts(ctx)
+    t1, waits1 = _syncs(ctx, outer.execute_device)
+    assert sorted_build_counts(ctx)[1] == fb0 + 1
+    t2, waits2 = _syncs(ctx, outer.execute_device)
+    assert sorted_build_counts(ctx)[1] == fb0 + 1
+    print("host waits: first execution", waits1, "second", waits2)
+    assert waits2 < waits1, (waits1, waits2)
+    for t in (t1, t2):
+        got = t.to_batches()
+        assert [b.num_rows for b in got] == [b.num_rows for b in want]
+        assert rows_of(got) == rows_of(want)
