@@ -197,7 +197,8 @@ typedef struct qhip_exec_stats {
                               * Hash join: bytes the probe kernel reads per PROBE row (key + fused-filter columns). */
   double build_ms;           /* aggregate through the wide-key stage: the stage's memset + kernel;
                               * hash join: key evaluation + table build, first launch .. probe kernel (main_kernel_ms is the
-                              * probe kernel alone, total_device_ms the whole call incl. pair emission) */
+                              * probe kernel alone, total_device_ms the whole call incl. pair emission); hash join through
+                              * the wide-key stage: the stage's memset + two kernels, which run before that first launch */
   int64_t build_rows;        /* hash join: rows of the build side */
   double build_bytes_per_row;/* hash join: bytes of build-side columns its key / fused-filter expressions read per row */
 } qhip_exec_stats;
@@ -233,6 +234,17 @@ int qhip_ctx_set_timing(qhip_ctx* ctx, int32_t on);
 int qhip_ctx_set_wide_group_keys(qhip_ctx* ctx, int32_t mode);
 /* aggregate calls of this context that went through the wide-key encoding stage so far */
 int64_t qhip_ctx_wide_key_aggregates(qhip_ctx* ctx);
+/* Wide join keys. The reference hashes join keys of any length and any number of columns and compares them on every probe hit
+ * (utils/array.rs:171-210, hash_join.rs:191-215); the join kernels pack a key into at most 8 words (a Utf8 key: 7 words, 55
+ * bytes) and answer QHIP_UNSUPPORTED beyond. With the switch on, a hash join whose keys on both sides are plain columns first
+ * replaces the key of either side by one 32-bit key code per row (exact: keys are compared, not only hashed; a row with a NULL
+ * key column matches nothing), joins on that code — every layout, join type, residual filter and deferred size as it is —
+ * and drops the code columns from the result. mode 0: off (the default); 1: when the packed key would not fit; 2: every hash
+ * join whose keys are plain columns (tests, fuzzing). Up to 32 key columns and 2^30 build rows; computed join keys are not
+ * encoded. While the mode was never set, the environment's QHIP_JOIN_WIDE_KEYS (0/1/2) is read per call. */
+int qhip_ctx_set_wide_join_keys(qhip_ctx* ctx, int32_t mode);
+/* hash join calls of this context that went through the wide-key encoding stage so far */
+int64_t qhip_ctx_wide_key_joins(qhip_ctx* ctx);
 /* Deferred sizing. A hash join normally waits for its pair total to size its output (one host round trip per join). It
  * also remembers, per join (expressions, join type, probe rows — not the data), how many pairs it produced. While
  * deferred sizes are allowed, an Inner join with such a hint does NOT wait: its output is allocated for the remembered

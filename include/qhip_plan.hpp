@@ -40,6 +40,9 @@ class Context {
   // GROUP BY keys that do not fit the packed key words are encoded to group codes first (qhip.h: 0 off, 1 when needed, 2 always)
   void set_wide_group_keys(int mode) const { check(qhip_ctx_set_wide_group_keys(ctx_, mode)); }
   int64_t wide_key_aggregates() const { return qhip_ctx_wide_key_aggregates(ctx_); }
+  // hash join keys that do not fit the packed key words are encoded to shared key codes first (qhip.h: 0 off, 1 when needed, 2 always)
+  void set_wide_join_keys(int mode) const { check(qhip_ctx_set_wide_join_keys(ctx_, mode)); }
+  int64_t wide_key_joins() const { return qhip_ctx_wide_key_joins(ctx_); }
 
  private:
   qhip_ctx* ctx_ = nullptr;

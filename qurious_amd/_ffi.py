@@ -136,6 +136,8 @@ def load_library() -> C.CDLL:
             "qhip_ctx_set_timing": (C.c_int, [vp, i32]),
             "qhip_ctx_set_wide_group_keys": (C.c_int, [vp, i32]),
             "qhip_ctx_wide_key_aggregates": (i64, [vp]),
+            "qhip_ctx_set_wide_join_keys": (C.c_int, [vp, i32]),
+            "qhip_ctx_wide_key_joins": (i64, [vp]),
             "qhip_ctx_allow_deferred_sizes": (C.c_int, [vp, i32]),
             "qhip_ctx_forget_plans": (C.c_int, [vp]),
             "qhip_ctx_device_name": (C.c_int, [vp, C.c_char_p, C.c_size_t]),
@@ -244,6 +246,16 @@ class Context:
     def wide_key_aggregates(self) -> int:
         """Aggregate calls of this context that went through the wide-key encoding stage so far."""
         return int(self.lib.qhip_ctx_wide_key_aggregates(self.handle))
+
+    def set_wide_join_keys(self, mode: int):
+        """Hash join keys wider than the packed 8 key words (long Utf8 values, many columns) are first encoded to one shared key
+        code per row of either side: 0 off, 1 when the key does not fit, 2 every hash join over plain key columns. Never set: the
+        environment's QHIP_JOIN_WIDE_KEYS decides per call (default 0)."""
+        self.check(self.lib.qhip_ctx_set_wide_join_keys(self.handle, int(mode)))
+
+    def wide_key_joins(self) -> int:
+        """Hash join calls of this context that went through the wide-key encoding stage so far."""
+        return int(self.lib.qhip_ctx_wide_key_joins(self.handle))
 
     def sync_count(self) -> int:
         """Host waits on the device made through the library so far (the difference around a plan = its round trips)."""

@@ -276,6 +276,11 @@ struct Ctx {
   // decides per call); the aggregate calls that went through the stage
   int wide_keys_mode = -1;
   int64_t wide_key_aggregates = 0;
+  // wide join keys (join.cpp maybe_encode_wide_join_key): qhip_ctx_set_wide_join_keys' mode, -1 = never set (QHIP_JOIN_WIDE_KEYS
+  // decides per call); the join calls that went through the stage; the stage's device time in the last join (timing on)
+  int wide_join_keys_mode = -1;
+  int64_t wide_key_joins = 0;
+  float wide_join_stage_ms = 0;
   // (total_out: the output table's own host word — the page-locked slot is part of a ring and is reused by later joins, so
   // the verified total is copied where the table can still find it however long it stays unsettled)
   struct PendingSize { uint32_t* slot; uint64_t key; uint64_t capacity; uint64_t dup_hint; std::shared_ptr<uint64_t> total_out; };

@@ -405,6 +405,14 @@ int qhip_ctx_set_wide_group_keys(qhip_ctx* ctx, int32_t mode) {
 
 int64_t qhip_ctx_wide_key_aggregates(qhip_ctx* ctx) { return ctx ? ctx->wide_key_aggregates : 0; }
 
+int qhip_ctx_set_wide_join_keys(qhip_ctx* ctx, int32_t mode) {
+  if (!ctx || mode < 0 || mode > 2) return QHIP_INVALID_ARGUMENT;
+  ctx->wide_join_keys_mode = mode;
+  return QHIP_OK;
+}
+
+int64_t qhip_ctx_wide_key_joins(qhip_ctx* ctx) { return ctx ? ctx->wide_key_joins : 0; }
+
 int qhip_ctx_allow_deferred_sizes(qhip_ctx* ctx, int32_t delta) {
   if (!ctx) return QHIP_INVALID_ARGUMENT;
   if (delta == 0) { ctx->allow_deferred_sizes = 0; ctx->pending_sizes.clear(); }   // reset (after an error above a deferred join)
@@ -467,7 +475,7 @@ int qhip_ctx_last_stats(const qhip_ctx* ctx, qhip_exec_stats* out) {
     if (sync_event(c->ev[1]) == hipSuccess && hipEventElapsedTime(&ms, c->ev[0], c->ev[1]) == hipSuccess) c->stats.total_device_ms = ms;
     if (c->stats_timing_pending >= 2 && hipEventElapsedTime(&ms, c->ev[2], c->ev[3]) == hipSuccess) c->stats.main_kernel_ms = ms;
     if (c->stats_timing_pending == 3 && hipEventElapsedTime(&ms, c->ev[0], c->ev[4]) == hipSuccess) c->stats.build_ms = ms;   // (partition: pass 1 + scan)
-    if (c->stats_timing_pending == 2 && hipEventElapsedTime(&ms, c->ev[0], c->ev[2]) == hipSuccess) c->stats.build_ms = ms;   // (hash join)
+    if (c->stats_timing_pending == 2 && hipEventElapsedTime(&ms, c->ev[0], c->ev[2]) == hipSuccess) c->stats.build_ms = c->wide_join_stage_ms > 0 ? c->wide_join_stage_ms : ms;   // (hash join; through the wide-key stage: the stage)
     else if (c->stats_timing_pending == 1) c->stats.main_kernel_ms = c->stats.total_device_ms;
     c->stats_timing_pending = 0;
   }

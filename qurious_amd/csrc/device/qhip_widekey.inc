@@ -121,3 +121,70 @@ QH_WK_HD inline unsigned qh_wk_insert(const qh_wk_col* cols, int ncols, unsigned
     s = (s + 1u) & slot_mask;
   }
 }
+
+// ---- join keys (join.cpp maybe_encode_wide_join_key, kernels_rel.hip k_widekey_join_build / k_widekey_join_lookup): the build
+// side's rows are inserted as above, the probe side's rows are then looked up in the finished table, so that both sides carry
+// codes of ONE numbering: build code == probe code <=> the keys are equal and non-NULL. In a join a NULL key never matches
+// (probe_hash_table, hash_join.rs:191-215), unlike GROUP BY where NULL is a value of its own.
+
+// any key column NULL in this row?
+QH_WK_HD inline bool qh_wk_any_null(const qh_wk_col* cols, int ncols, unsigned row) {
+  for (int k = 0; k < ncols; ++k)
+    if (!qh_wk_valid(cols[k], row)) return true;
+  return false;
+}
+
+// qh_wk_equal with row a read through colsA and row b through colsB (the same types column by column: the host checks that).
+// Both rows are known to have no NULL key column. Same masked-tail Utf8 word reads, same slack behind the data buffers.
+QH_WK_HD inline bool qh_wk_equal2(const qh_wk_col* colsA, const qh_wk_col* colsB, int ncols, unsigned a, unsigned b) {
+  for (int k = 0; k < ncols; ++k) {
+    const qh_wk_col& ca = colsA[k];
+    const qh_wk_col& cb = colsB[k];
+    if (ca.width == 0) {
+      const int* offa = (const int*)ca.v;
+      const int* offb = (const int*)cb.v;
+      const unsigned oa = (unsigned)offa[a], la = (unsigned)offa[a + 1] - oa;
+      const unsigned ob = (unsigned)offb[b], lb = (unsigned)offb[b + 1] - ob;
+      if (la != lb) return false;
+      const unsigned nw = (la + 7) >> 3;
+      for (unsigned w = 0; w < nw; ++w)
+        if (qh_wk_str_word(ca.d + oa, la, w) != qh_wk_str_word(cb.d + ob, la, w)) return false;
+    } else if (ca.width == 16) {
+      const unsigned long long* va = (const unsigned long long*)ca.v + 2 * (unsigned long long)a;
+      const unsigned long long* vb = (const unsigned long long*)cb.v + 2 * (unsigned long long)b;
+      if (va[0] != vb[0] || va[1] != vb[1]) return false;
+    } else if (qh_wk_word(ca, a) != qh_wk_word(cb, b)) {
+      return false;
+    }
+  }
+  return true;
+}
+
+// The code of a BUILD row: a row with a NULL key column is not inserted and is its own code (unique, and no inserted key's:
+// a representative is always a row without NULLs); every other row is inserted as above. Codes lie in [0, build rows).
+template <class A>
+QH_WK_HD inline unsigned qh_wk_join_build_row(const qh_wk_col* cols, int ncols, unsigned long long* table, unsigned slot_mask,
+                                              unsigned long long hash_mask, unsigned row) {
+  if (qh_wk_any_null(cols, ncols, row)) return row;
+  return qh_wk_insert<A>(cols, ncols, table, slot_mask, hash_mask, row);
+}
+
+// The code of a PROBE row: the build row that represents its key, -1 when a key column is NULL or no build row has the key.
+// The table is complete and read-only here. The hash of equal non-NULL keys is the same through either side's descriptors.
+template <class A>
+QH_WK_HD inline int qh_wk_join_lookup_row(const qh_wk_col* pcols, const qh_wk_col* bcols, int ncols, const unsigned long long* table,
+                                          unsigned slot_mask, unsigned long long hash_mask, unsigned row) {
+  if (qh_wk_any_null(pcols, ncols, row)) return -1;
+  const unsigned long long h = qh_wk_hash(pcols, ncols, row) & hash_mask;
+  const unsigned tag = (unsigned)(h >> 32);
+  unsigned s = (unsigned)h & slot_mask;
+  for (;;) {
+    const unsigned long long cur = A::load(table + s);
+    if (cur == 0) return -1;
+    if ((unsigned)(cur >> 32) == tag) {
+      const unsigned other = (unsigned)cur - 1u;
+      if (qh_wk_equal2(pcols, bcols, ncols, row, other)) return (int)other;
+    }
+    s = (s + 1u) & slot_mask;
+  }
+}

@@ -15,6 +15,8 @@
 //
 // hash_join (the driver, at the end of the file) is the operator's outline: a loop over ATTEMPTS, every stage a function of
 // this file. A stage that finds that the attempt cannot go on returns why (Repeat) and the driver starts the next one from the top:
+//    0  maybe_encode_wide_join_key   (once, in front of the driver) a key that does not fit the packed key words: one shared
+//                                  key code per row of either side, then the driver below on the codes
 //    1  validate_join_args
 //    2  choose_dense_candidate     the build key's range: direct-address table?
 //    3  resolve_join_inputs        deferred columns, Utf8 key lengths of both sides, narrow copies; check_scan_filters
@@ -90,6 +92,9 @@ struct JoinTuning {
   uint64_t probe_tiles_per_wave;   // QHIP_PROBE_TILES_PER_WAVE (>= 1): most tiles a probe wavefront owns (measurement)
   bool eager_gather;          // QHIP_EAGER_GATHER=1: output columns gathered at once, not when first read (test forcing)
   bool eager_offsets;         // QHIP_EAGER_OFFSETS=1: the output's batch offsets fetched at once (test forcing)
+  int wide_keys;              // QHIP_JOIN_WIDE_KEYS 0 never / 1 when the packed key does not fit / 2 every hash join over plain key columns:
+                              // keys of both sides encoded to shared key codes first (policy, off; 2 = tests) — the context's own mode goes first
+  int wide_key_hash_bits;     // QHIP_JOIN_WIDE_KEY_HASH_BITS (1..63): only so many bits of the encoding's hash (test forcing: long probe chains)
 };
 JoinTuning read_join_tuning() {
   JoinTuning t;
@@ -114,6 +119,8 @@ JoinTuning read_join_tuning() {
   t.probe_tiles_per_wave = (uint64_t)std::max(1, env_int("QHIP_PROBE_TILES_PER_WAVE", 32));
   t.eager_gather = env_int("QHIP_EAGER_GATHER", 0) != 0;
   t.eager_offsets = env_int("QHIP_EAGER_OFFSETS", 0) != 0;
+  t.wide_keys = env_int("QHIP_JOIN_WIDE_KEYS", 0);
+  t.wide_key_hash_bits = env_int("QHIP_JOIN_WIDE_KEY_HASH_BITS", 0);
   return t;
 }
 
@@ -832,7 +839,8 @@ void set_join_stats(Ctx* ctx, const JoinArgs& a, const JoinCall& c, const JoinRu
 }
 
 // ---------------------------------------------------------------- the driver
-qhip_table* hash_join(Ctx* ctx, const JoinArgs& a) {
+// (first: the switches as the caller has just read them, for the first attempt — one look at the environment per call)
+qhip_table* hash_join(Ctx* ctx, const JoinArgs& a, const JoinTuning* first = nullptr) {
   bool dense_off = false;   // the dense layout is switched off for the attempts that follow one whose dense table did not fit
   // An attempt that cannot go on says why and the next one starts from the top. The loop ends because each reason removes its own
   // cause: settling drops L->rows_dev; "dense does not fit" sets dense_off; a build side found out of order or with duplicate keys
@@ -849,7 +857,7 @@ qhip_table* hash_join(Ctx* ctx, const JoinArgs& a) {
     // a probe side of deferred size is made exact first; a build side of deferred size is read as it is when the region
     // build takes it (qk_join_scatter stops at the device-side row count), else it is made exact too (settle_build_side)
     settle_rows(a.R);
-    const JoinTuning t = read_join_tuning();
+    const JoinTuning t = first && why == Repeat::No ? *first : read_join_tuning();
     JoinCall c;
     JoinRun r;
     set_join_type_flags(a, c);
@@ -909,6 +917,181 @@ qhip_table* hash_join(Ctx* ctx, const JoinArgs& a) {
   }
 }
 
+
+// ---------------------------------------------------------------- stage 0: wide join keys
+// The reference hashes join keys of any length and any number of columns (utils/array.rs:171-210) and compares them on every
+// probe hit (hash_join.rs:191-215); a packed join key has 8 words (a Utf8 key 7 of them). A key that does not fit never reaches
+// the join: k_widekey_join_build gives every build row the number of ONE build row with the same key, k_widekey_join_lookup gives
+// every probe row the number of the build row that represents its key, or -1 (device/qhip_widekey.inc) — exact, the keys
+// themselves are compared; a row with a NULL key column matches nothing — and hash_join runs, with all its layouts, join types,
+// residual filter, deferred sizes and output order, over views of both sides whose one key is that Int32 column. The build
+// codes lie in [0, B), which the view says (ColRange), so the direct-address layout is taken without a reduction. 16 bytes of
+// HBM per BUILD row (the slot table, twice the rows) while the stage runs + 4 per row of either side for the codes. Rows a fused
+// scan filter rejects are encoded for nothing; a rejected build row may be a key's representative: the code is only a label.
+// mode 1: when the packed key does not fit; 2: every hash join whose keys on both sides are plain columns (tests, fuzzing).
+// Runs ONCE per call, outside the driver's attempts. Returns the result, or nullptr when the join runs on its keys as they are.
+bool plain_column_keys(const qhip_table* t, const qhip_expr* ex, int nex, const int32_t* on, int n_on) {
+  for (int k = 0; k < n_on; ++k) {
+    if (on[k] < 0 || on[k] >= nex) return false;
+    const qhip_expr& e = ex[on[k]];
+    if (e.kind != QHIP_EXPR_COLUMN || e.column < 0 || e.column >= (int)t->cols.size()) return false;
+  }
+  return true;
+}
+bool plain_join_keys(const JoinArgs& a) {
+  return a.n_on > 0 && a.on_l && a.on_r && plain_column_keys(a.L, a.lex, a.nlex, a.on_l, a.n_on) && plain_column_keys(a.R, a.rex, a.nrex, a.on_r, a.n_on);
+}
+
+// one side of the coded join: the side's columns + its code column, the key expression array with ONE key root
+struct CodedSide {
+  qhip_table view;
+  std::vector<qhip_expr> ex;
+  int32_t root = 0;
+};
+void make_coded_side(Ctx* ctx, const qhip_table* t, const qhip_expr* ex, int nex, int pred, const std::shared_ptr<DevBuf>& code, CodedSide& out) {
+  qhip_table& v = out.view;
+  v.ctx = ctx;
+  v.names = t->names;
+  v.nullable = t->nullable;
+  v.cols = t->cols;
+  v.num_rows = t->num_rows;
+  v.batch_offsets = t->batch_offsets;        // (the batch structure as it is, fetched or not)
+  v.pending_offsets = t->pending_offsets;
+  v.offsets_dev = t->offsets_dev;
+  DevColumn cc;
+  cc.type = DType(QHIP_INT32); cc.length = t->num_rows; cc.values = code;
+  v.names.push_back("key_code");
+  v.nullable.push_back(false);
+  v.cols.push_back(std::move(cc));
+  out.ex.assign(ex, ex + nex);
+  qhip_expr ce;
+  memset(&ce, 0, sizeof ce);
+  ce.kind = QHIP_EXPR_COLUMN; ce.column = (int32_t)t->cols.size(); ce.left = ce.right = ce.third = -1;
+  // The key columns' own nodes stay in the array. Whatever the scan filter does not reach must not count as a reference any
+  // more — the join gathers or uploads the columns its expression arrays name — so those Column nodes now name the code column.
+  std::vector<char> reached((size_t)nex, 0);
+  std::vector<int32_t> todo;
+  if (pred >= 0) todo.push_back(pred);
+  while (!todo.empty()) {
+    const int32_t k = todo.back();
+    todo.pop_back();
+    if (k < 0 || k >= nex || reached[(size_t)k]) continue;
+    reached[(size_t)k] = 1;
+    todo.push_back(out.ex[(size_t)k].left); todo.push_back(out.ex[(size_t)k].right); todo.push_back(out.ex[(size_t)k].third);
+  }
+  for (int k = 0; k < nex; ++k)
+    if (!reached[(size_t)k] && out.ex[(size_t)k].kind == QHIP_EXPR_COLUMN) out.ex[(size_t)k].column = ce.column;
+  out.ex.push_back(ce);
+  out.root = nex;
+}
+
+qhip_table* maybe_encode_wide_join_key(Ctx* ctx, const JoinTuning& tune, int mode, const JoinArgs& a) {
+  if (mode <= 0 || !plain_join_keys(a)) return nullptr;
+  const int n = a.n_on;
+  validate_join_args(a);
+  QHIP_HIP_CHECK(hipSetDevice(ctx->device));
+  settle_rows(a.R);   // (as the driver does first)
+  std::vector<int32_t> lkeys((size_t)n), rkeys((size_t)n);
+  for (int k = 0; k < n; ++k) { lkeys[(size_t)k] = a.lex[a.on_l[k]].column; rkeys[(size_t)k] = a.rex[a.on_r[k]].column; }
+  if (mode == 1) {   // (what resolve_join_inputs is about to do anyway: nothing is gathered or measured twice)
+    resolve_referenced(ctx, a.L, a.lex, a.nlex, true);
+    resolve_referenced(ctx, a.R, a.rex, a.nrex);
+    std::vector<InputCol> lc = input_cols_of(a.L, true), rc = input_cols_of(a.R);
+    ensure_utf8_key_lengths(ctx, a.L, a.lex, a.nlex, a.on_l, n, lc);
+    ensure_utf8_key_lengths(ctx, a.R, a.rex, a.nrex, a.on_r, n, rc);
+    for (int k = 0; k < n; ++k) {
+      InputCol &l = lc[(size_t)lkeys[(size_t)k]], &r = rc[(size_t)rkeys[(size_t)k]];
+      l.utf8_max_len = r.utf8_max_len = std::max(l.utf8_max_len, r.utf8_max_len);
+      l.has_nulls = r.has_nulls = false;   // (a join key has no null-mask word: plan_keys lays it out without one)
+    }
+    if (packed_key_fits(lc, lkeys.data(), n) && packed_key_fits(rc, rkeys.data(), n)) return nullptr;
+  }
+  // the errors the join raises, with its texts, before any kernel of the stage: scan filters, expression typing, key types
+  check_scan_filters(a);
+  {
+    ExprSet les, res;
+    les.build(a.lex, a.nlex, input_cols_of(a.L));
+    res.build(a.rex, a.nrex, input_cols_of(a.R));
+    for (int k = 0; k < n; ++k) check_key_type(les.at(a.on_l[k]).type);
+    for (int k = 0; k < n; ++k) check_key_type(res.at(a.on_r[k]).type);
+    for (int k = 0; k < n; ++k)
+      if (les.at(a.on_l[k]).type != res.at(a.on_r[k]).type)   // arrow's eq (hash_join.rs:203) needs identical types
+        fail(QHIP_INVALID_ARGUMENT, "Invalid argument error: Invalid comparison operation: " + dtype_name(les.at(a.on_l[k]).type) + " == " +
+                                        dtype_name(res.at(a.on_r[k]).type));
+  }
+  if (n > kWideKeyCols) fail(QHIP_UNSUPPORTED, "join key of more than 32 columns is not accelerated");
+  // 1. exact row counts, the key columns materialised
+  settle_rows(a.L);
+  const int64_t B = a.L->num_rows, P = a.R->num_rows;
+  if (B > ((int64_t)1 << 30)) fail(QHIP_UNSUPPORTED, "wide join key over more than 2^30 build rows is not accelerated");
+  WideKeyCols bk, pk;
+  memset(&bk, 0, sizeof bk);
+  memset(&pk, 0, sizeof pk);
+  auto describe = [&](const qhip_table* t, const std::vector<int32_t>& keys, WideKeyCols& wk) {
+    for (int k = 0; k < n; ++k) {
+      const DevColumn& c = resolved(ctx, t->cols[(size_t)keys[(size_t)k]]);
+      WideKeyCol& d = wk.c[k];
+      d.v = c.values ? c.values->ptr : nullptr;
+      d.d = c.data ? c.data->as<uint8_t>() : nullptr;
+      d.n = c.validity ? c.validity->as<uint8_t>() : nullptr;
+      d.width = (uint32_t)dtype_width(c.type);   // (0: Utf8 — check_key_type has let nothing else without a width through)
+    }
+  };
+  if (B > 0) describe(a.L, lkeys, bk);
+  if (P > 0) describe(a.R, rkeys, pk);
+  // 2. the codes
+  auto bcode = std::make_shared<DevBuf>((size_t)B * 4), pcode = std::make_shared<DevBuf>((size_t)P * 4);
+  const uint32_t nslots = std::max<uint32_t>(1024, pow2_ceil32((uint64_t)std::max<int64_t>(B, 1) * 2));
+  struct Events {   // (timings asked for: a pair of the stage's own — the join behind it records the context's)
+    hipEvent_t e[2] = {nullptr, nullptr};
+    ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
+    hipEvent_t operator[](int k) const { return e[k]; }
+  } ev;
+  if (ctx->timing) for (hipEvent_t& e : ev.e) { QHIP_HIP_CHECK(hipEventCreate(&e)); }
+  if (B > 0 || P > 0) {
+    DevBuf table((size_t)nslots * 8);
+    const int bits = tune.wide_key_hash_bits;
+    const uint64_t hash_mask = bits > 0 && bits < 64 ? (1ULL << bits) - 1 : ~0ULL;
+    if (ev[0]) (void)hipEventRecord(ev[0], ctx->stream);
+    QHIP_HIP_CHECK(hipMemsetAsync(table.ptr, 0, (size_t)nslots * 8, ctx->stream));
+    launch_widekey_join_build(bk, n, table.as<uint64_t>(), nslots, hash_mask, bcode->as<int32_t>(), (uint64_t)B, ctx->stream);
+    launch_widekey_join_lookup(pk, bk, n, table.as<uint64_t>(), nslots, hash_mask, pcode->as<int32_t>(), (uint64_t)P, ctx->stream);
+    if (ev[1]) (void)hipEventRecord(ev[1], ctx->stream);
+    // (the table goes back to the pool here; whoever gets it next runs on the same stream, i.e. afterwards)
+  }
+  // 3. both sides' columns + their code column; 4. the one key of either side is that column
+  CodedSide ls, rs;
+  make_coded_side(ctx, a.L, a.lex, a.nlex, a.lpred, bcode, ls);
+  make_coded_side(ctx, a.R, a.rex, a.nrex, a.rpred, pcode, rs);
+  {   // the build codes' range by construction: the direct-address layout without a reduction and a host wait
+    ColRange& range = *ls.view.cols.back().range;
+    range.known = true; range.min = 0; range.max = std::max<int64_t>(B - 1, 0); range.ascending = false;
+  }
+  JoinArgs c = a;
+  c.L = &ls.view; c.R = &rs.view;
+  c.lex = ls.ex.data(); c.nlex = (int)ls.ex.size();
+  c.rex = rs.ex.data(); c.nrex = (int)rs.ex.size();
+  c.on_l = &ls.root; c.on_r = &rs.root; c.n_on = 1;
+  // 5. the join itself, unchanged (scan filters, residual filter and join type as they came). The dense Inner join's key
+  // materialisation (materializes_key) asks for an Int64 key column: never taken for the Int32 codes.
+  std::unique_ptr<qhip_table> out(hash_join(ctx, c, &tune));
+  ++ctx->wide_key_joins;
+  if (ev[0] && ev[1] && (B > 0 || P > 0)) {   // the stage's memset + two kernels, in the statistics' build_ms
+    float ms = 0;
+    if (sync_event(ev[1]) == hipSuccess && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) ctx->wide_join_stage_ms = ms;
+  }
+  // 6. without the code columns (deferred gathers nobody has read): [L | code | R | code] -> [L | R]
+  auto drop = [&](size_t at) {
+    out->cols.erase(out->cols.begin() + (std::ptrdiff_t)at);
+    out->names.erase(out->names.begin() + (std::ptrdiff_t)at);
+    out->nullable.erase(out->nullable.begin() + (std::ptrdiff_t)at);
+  };
+  const size_t nl = a.L->cols.size(), nr = a.R->cols.size();
+  if (out->cols.size() > nl + 1) drop(nl + 1 + nr);   // (join types that emit the probe side)
+  drop(nl);
+  return out.release();
+}
+
 }  // namespace
 
 extern "C" int qhip_hash_join_execute(qhip_ctx* ctx, const qhip_table* left, const qhip_table* right, int32_t join_type,
@@ -922,7 +1105,20 @@ extern "C" int qhip_hash_join_execute(qhip_ctx* ctx, const qhip_table* left, con
                       filter_root, filter_sides, filter_cols, n_filter_cols, left_scan_filter_root, right_scan_filter_root};
   return guarded(ctx, [&] {
     try {
-      *out = hash_join(ctx, a);
+      ctx->wide_join_stage_ms = 0;
+      const JoinTuning tune = read_join_tuning();
+      const int wide_mode = ctx->wide_join_keys_mode >= 0 ? ctx->wide_join_keys_mode : tune.wide_keys;
+      if (wide_mode > 0 && (*out = maybe_encode_wide_join_key(ctx, tune, wide_mode, a))) return;
+      try {
+        *out = hash_join(ctx, a, &tune);
+      } catch (const Error& e) {
+        // wide keys are on, yet the key that does not fit is computed: the encoding stage takes plain key columns only
+        const std::string what = e.what();
+        if (wide_mode == 1 && e.code == QHIP_UNSUPPORTED && !plain_join_keys(a) &&
+            (what.find("wider than 8 words") != std::string::npos || what.find("longer than 55 bytes") != std::string::npos))
+          fail(QHIP_UNSUPPORTED, what + " (wide join keys: computed join keys are not encoded)");
+        throw;
+      }
     } catch (...) {
       ctx->pending_sizes.clear();   // (joins of deferred size below: whatever they left is void with this call's input)
       throw;

@@ -136,4 +136,12 @@ struct WideKeyCols { WideKeyCol c[kWideKeyCols]; };
 // table: nslots (a power of two >= 2 * nrows) zeroed 8-byte slots; code[row] = the representative row of the row's key
 void launch_widekey_encode(const WideKeyCols& cols, int ncols, uint64_t* table, uint32_t nslots, uint64_t hash_mask, int32_t* code, uint64_t nrows,
                            hipStream_t s);
+// ... and wide JOIN keys -> codes of one numbering for both sides (k_widekey_join_build over the build rows, then
+// k_widekey_join_lookup over the probe rows on the same stream; join.cpp maybe_encode_wide_join_key). Grid-stride launches of
+// at most kWideKeyGridCap workgroups of QH_BLOCK threads.
+constexpr unsigned kWideKeyGridCap = 8192;
+void launch_widekey_join_build(const WideKeyCols& cols, int ncols, uint64_t* table, uint32_t nslots, uint64_t hash_mask, int32_t* code, uint64_t nrows,
+                               hipStream_t s);
+void launch_widekey_join_lookup(const WideKeyCols& probe_cols, const WideKeyCols& build_cols, int ncols, const uint64_t* table, uint32_t nslots,
+                                uint64_t hash_mask, int32_t* code, uint64_t nrows, hipStream_t s);
 }  // namespace qhip

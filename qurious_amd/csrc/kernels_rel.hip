@@ -1422,6 +1422,41 @@ void launch_widekey_encode(const WideKeyCols& cols, int ncols, uint64_t* table, 
                      (u64)nrows);
 }
 
+// ---- wide JOIN keys -> one shared numbering of both sides (join.cpp maybe_encode_wide_join_key). The build kernel is the
+// encoding above without the rows that have a NULL key column; the lookup kernel runs behind it on the same stream, on a
+// table that no longer changes: plain loads, no atomics. The table is sized from the build side alone (16 bytes per build row).
+struct WkSlotPlain {
+  static __device__ __forceinline__ u64 load(const u64* p) { return *p; }
+};
+__global__ __launch_bounds__(QH_BLOCK) void k_widekey_join_build(WideKeyColsArg cols, int ncols, u64* table, u32 slot_mask, u64 hash_mask, u32* code, u64 nrows) {
+  const u64 stride = (u64)gridDim.x * QH_BLOCK;
+  for (u64 row = (u64)blockIdx.x * QH_BLOCK + threadIdx.x; row < nrows; row += stride)
+    code[row] = qh_wk_join_build_row<WkSlotHbm>(cols.c, ncols, table, slot_mask, hash_mask, (u32)row);
+}
+__global__ __launch_bounds__(QH_BLOCK) void k_widekey_join_lookup(WideKeyColsArg pcols, WideKeyColsArg bcols, int ncols, const u64* table, u32 slot_mask,
+                                                                  u64 hash_mask, int* code, u64 nrows) {
+  const u64 stride = (u64)gridDim.x * QH_BLOCK;
+  for (u64 row = (u64)blockIdx.x * QH_BLOCK + threadIdx.x; row < nrows; row += stride)
+    code[row] = qh_wk_join_lookup_row<WkSlotPlain>(pcols.c, bcols.c, ncols, table, slot_mask, hash_mask, (u32)row);
+}
+void launch_widekey_join_build(const WideKeyCols& cols, int ncols, uint64_t* table, uint32_t nslots, uint64_t hash_mask, int32_t* code, uint64_t nrows,
+                               hipStream_t s) {
+  if (!nrows) return;
+  WideKeyColsArg a;
+  memcpy(&a, &cols, sizeof a);
+  hipLaunchKernelGGL(k_widekey_join_build, dim3(grid_for(nrows, QH_BLOCK, kWideKeyGridCap)), dim3(QH_BLOCK), 0, s, a, ncols, (u64*)table, nslots - 1u,
+                     (u64)hash_mask, (u32*)code, (u64)nrows);
+}
+void launch_widekey_join_lookup(const WideKeyCols& probe_cols, const WideKeyCols& build_cols, int ncols, const uint64_t* table, uint32_t nslots,
+                                uint64_t hash_mask, int32_t* code, uint64_t nrows, hipStream_t s) {
+  if (!nrows) return;
+  WideKeyColsArg p, b;
+  memcpy(&p, &probe_cols, sizeof p);
+  memcpy(&b, &build_cols, sizeof b);
+  hipLaunchKernelGGL(k_widekey_join_lookup, dim3(grid_for(nrows, QH_BLOCK, kWideKeyGridCap)), dim3(QH_BLOCK), 0, s, p, b, ncols, (const u64*)table, nslots - 1u,
+                     (u64)hash_mask, (int*)code, (u64)nrows);
+}
+
 // stable sort of (key, value) pairs on the low `bits` bits of the key (rocPRIM LSD radix sort): groups build rows by
 // hash-table slot / rows by partition id while keeping ascending row order inside a group
 void stable_sort_pairs_u32(const uint32_t* keys_in, uint32_t* keys_out, const uint32_t* vals_in, uint32_t* vals_out, uint64_t n, int bits,

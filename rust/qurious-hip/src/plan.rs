@@ -71,6 +71,9 @@ impl HipContext {
         // GROUP BY keys of any width, as the reference hashes them (utils/array.rs:171-210): keys that do not fit the packed
         // key words are encoded to group codes first instead of sending the aggregate back to the CPU node
         unsafe { qhip_ctx_set_wide_group_keys(raw, 1) };
+        // Join keys of any width too, as HashJoinExec hashes and compares them (hash_join.rs:191-215): both sides are encoded
+        // to shared key codes first instead of keeping the single-threaded CPU join
+        unsafe { qhip_ctx_set_wide_join_keys(raw, 1) };
         Ok(Arc::new(Self { raw, lock: Mutex::new(()), tables: Mutex::new(HashMap::new()) }))
     }
     pub fn raw(&self) -> *mut qhip_ctx {
