@@ -289,6 +289,28 @@ int qhip_table_from_arrow(qhip_ctx* ctx, const struct ArrowSchema* schema,
  * slot for but never uses (physical/plan/scan.rs:12-17, planner/mod.rs:251-256). */
 int qhip_table_from_arrow_lazy(qhip_ctx* ctx, const struct ArrowSchema* schema, struct ArrowArray* const* batches,
                                int64_t n_batches, qhip_table** out);
+/* Decode a CSV file's text ON THE DEVICE into a table (csrc/csv.cpp; replaces datasource/file/csv.rs:33-70 + the
+ * upload). bytes: the file's contents in host memory, read only during the call. schema: a struct ArrowSchema naming EVERY
+ * field of a record, in order. columns / n_columns: the fields to decode, in output order (NULL / 0 = all); a field that is not
+ * projected is never parsed. batch_rows: a batch boundary every batch_rows rows (<= 0: one batch).
+ * The call is eager and exact or not at all: QHIP_OK with a table whose columns are what qhip_table_from_arrow would hold after
+ * a host parse of the same bytes (Arrow C++ with this schema), or QHIP_UNSUPPORTED with nothing created — the message names the
+ * first reason and the record — and the caller takes the host path. Outside the device's grammar ("needs host"): any quote
+ * byte, a '\r' without '\n', a byte order mark, an empty file, an empty line, a short or long record, a header that differs
+ * from the schema's names, escape >= 0, a projected column that is not Int8..Int64, UInt8..UInt64, Float64, Date32,
+ * Decimal128(p, s >= 0) or Utf8, and every field spelling outside the strict grammar of csrc/device/qhip_csv.inc. */
+typedef struct qhip_csv_options {
+  int32_t has_header;   /* skip the first record (its names must equal the schema's) */
+  int32_t delimiter;    /* one byte, e.g. ',' or '|' */
+  int32_t quote;        /* the byte that makes a file "not plain" (usually '"'); -1: none */
+  int32_t escape;       /* -1: none; anything else -> QHIP_UNSUPPORTED */
+} qhip_csv_options;
+int qhip_table_from_csv(qhip_ctx* ctx, const struct ArrowSchema* schema, const void* bytes, int64_t n_bytes,
+                        const qhip_csv_options* options, const int32_t* columns, int32_t n_columns,
+                        int64_t batch_rows, qhip_table** out);
+/* Device time (ms) of the last qhip_table_from_csv's five passes — upload, scan, record starts, decode, Utf8 — when the
+ * context's timing is on (qhip_ctx_set_timing); zeros otherwise. n_out must be 5. */
+int qhip_ctx_csv_pass_ms(const qhip_ctx* ctx, double* out, int32_t n_out);
 /* Download batch `batch_index` as a struct ArrowArray (+ schema if out_schema != NULL).
  * Buffers are library-owned host memory freed by the release callbacks.
  * batch_index == -1: every row of the table as ONE array — a caller facing thousands of small batches (the reference's

@@ -9,7 +9,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import threading
-from typing import List
+from typing import List, Optional, Sequence
 
 import pyarrow as pa
 
@@ -88,6 +88,10 @@ class qhip_exec_stats(C.Structure):
     ]
 
 
+class qhip_csv_options(C.Structure):
+    _fields_ = [("has_header", C.c_int32), ("delimiter", C.c_int32), ("quote", C.c_int32), ("escape", C.c_int32)]
+
+
 class ArrowSchemaStruct(C.Structure):
     pass
 
@@ -143,6 +147,8 @@ def load_library() -> C.CDLL:
             "qhip_ctx_device_name": (C.c_int, [vp, C.c_char_p, C.c_size_t]),
             "qhip_table_from_arrow": (C.c_int, [vp, vp, P(vp), i64, P(vp)]),
             "qhip_table_from_arrow_lazy": (C.c_int, [vp, vp, P(vp), i64, P(vp)]),
+            "qhip_table_from_csv": (C.c_int, [vp, vp, vp, i64, P(qhip_csv_options), P(i32), i32, i64, P(vp)]),
+            "qhip_ctx_csv_pass_ms": (C.c_int, [vp, P(C.c_double), i32]),
             "qhip_table_to_arrow": (C.c_int, [vp, vp, i64, vp, vp]),
             "qhip_table_num_batches": (i64, [vp]),
             "qhip_table_batch_offsets": (C.c_int, [vp, P(i64), i64]),
@@ -257,6 +263,12 @@ class Context:
         """Hash join calls of this context that went through the wide-key encoding stage so far."""
         return int(self.lib.qhip_ctx_wide_key_joins(self.handle))
 
+    def csv_pass_ms(self) -> List[float]:
+        """Device time (ms) of the last device CSV decode's passes: upload, scan, record starts, decode, Utf8 (timing on)."""
+        out = (C.c_double * 5)()
+        self.check(self.lib.qhip_ctx_csv_pass_ms(self.handle, out, 5))
+        return list(out)
+
     def sync_count(self) -> int:
         """Host waits on the device made through the library so far (the difference around a plan = its round trips)."""
         return int(self.lib.qhip_ctx_sync_count(self.handle))
@@ -349,6 +361,26 @@ class DeviceTable:
             _release_schema(c_schema)
             for a in arrays:
                 _release_array(a)
+
+    @staticmethod
+    def from_csv_bytes(ctx: Context, schema: pa.Schema, data, has_header: bool = True, delimiter: str = ",", quote: Optional[str] = '"',
+                       escape: Optional[str] = None, columns: Optional[Sequence[int]] = None, batch_rows: Optional[int] = None) -> "DeviceTable":
+        """Decode a CSV file's bytes on the device (qhip_table_from_csv). `schema` names every field of a record; `columns` are
+        the field indices to decode, in output order (None = all). `data`: bytes, or anything with the buffer protocol (an
+        mmap). Raises UnsupportedError when the file lies outside the device's grammar — the caller then parses on the host."""
+        buf = pa.py_buffer(data)   # (zero copy, read-only buffers too; alive until the call returns)
+        n, addr = buf.size, (C.c_void_p(buf.address) if buf.size else None)
+        opt = qhip_csv_options(1 if has_header else 0, ord(delimiter), ord(quote) if quote else -1, ord(escape) if escape else -1)
+        cols = (C.c_int32 * max(1, len(columns or [])))(*[int(c) for c in (columns or [])])
+        c_schema = ArrowSchemaStruct()
+        schema._export_to_c(C.addressof(c_schema))
+        try:
+            out = C.c_void_p()
+            ctx.check(ctx.lib.qhip_table_from_csv(ctx.handle, C.addressof(c_schema), addr, n, C.byref(opt), cols if columns else None,
+                                                  len(columns or []), int(batch_rows or 0), C.byref(out)))
+            return DeviceTable(ctx, out)
+        finally:
+            _release_schema(c_schema)
 
     def forget_statistics(self):
         """drop the column statistics and narrow copies libqhip has collected on this table (qhip_table_forget_statistics)"""

@@ -281,6 +281,8 @@ struct Ctx {
   int wide_join_keys_mode = -1;
   int64_t wide_key_joins = 0;
   float wide_join_stage_ms = 0;
+  // device time of the last qhip_table_from_csv's passes (csv.cpp; timing on): upload, scan, record starts, decode, Utf8
+  float csv_pass_ms[5] = {0, 0, 0, 0, 0};
   // (total_out: the output table's own host word — the page-locked slot is part of a ring and is reused by later joins, so
   // the verified total is copied where the table can still find it however long it stays unsettled)
   struct PendingSize { uint32_t* slot; uint64_t key; uint64_t capacity; uint64_t dup_hint; std::shared_ptr<uint64_t> total_out; };

@@ -144,4 +144,18 @@ void launch_widekey_join_build(const WideKeyCols& cols, int ncols, uint64_t* tab
                                hipStream_t s);
 void launch_widekey_join_lookup(const WideKeyCols& probe_cols, const WideKeyCols& build_cols, int ncols, const uint64_t* table, uint32_t nslots,
                                 uint64_t hash_mask, int32_t* code, uint64_t nrows, hipStream_t s);
+// ---- CSV text -> typed columns (kernels_csv.hip, device/qhip_csv.inc; csv.cpp qhip_table_from_csv)
+struct CsvCol { void* values; uint64_t* valid; uint64_t* strpos; uint32_t field; uint8_t kind, width, a, b; };   // = qh_csv_col
+constexpr int kCsvCols = 64;
+struct CsvCols { CsvCol c[kCsvCols]; };
+constexpr uint64_t kCsvChunk = 16384;   // bytes of the file per workgroup of the two scan passes
+// counts[chunk] = record ends ('\n') in the file's chunk, *total += them; *err = min((position << 8) | reason) over the quote
+// bytes, lone '\r' and empty lines of [d0, n). counts: ceil(n / kCsvChunk) + 1 words.
+void launch_csv_scan(const uint8_t* buf, uint64_t d0, uint64_t n, int quote, uint32_t* counts, uint64_t* err, uint64_t* total, hipStream_t s);
+// starts[0] = d0, starts[1 + k] = one past the k-th '\n' of [d0, n); tail: starts[1 + number of '\n'] = n + 1
+void launch_csv_starts(const uint8_t* buf, uint64_t d0, uint64_t n, const uint32_t* chunk_offsets, uint64_t* starts, bool tail, hipStream_t s);
+// cols: ascending by field. *err = min((row << 8) | reason); null_counts / utf8_bytes: one zeroed u64 per descriptor
+void launch_csv_decode(const uint8_t* buf, uint64_t n, const uint64_t* starts, uint64_t nrec, const CsvCols& cols, int ncols, uint32_t nfields, int delim,
+                       uint64_t* err, uint64_t* null_counts, uint64_t* utf8_bytes, hipStream_t s);
+void launch_csv_copy_utf8(const uint8_t* buf, const uint64_t* strpos, const uint32_t* offsets, uint64_t nrows, uint8_t* data, hipStream_t s);
 }  // namespace qhip

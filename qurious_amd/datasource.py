@@ -7,6 +7,9 @@ an operator or an export reads it (qhip_table_from_arrow_lazy), so the columns a
 for TPC-H Q1 that is 7 of lineitem's 16 columns. Parquet additionally skips the untouched column chunks on disk when a
 `columns=` subset is requested up front.
 
+CSV files can instead be decoded ON THE DEVICE (`read_csv(device=True)` / QHIP_CSV_DEVICE=1, off by default): the
+text crosses PCIe once and unread columns are never parsed; a file outside the device's strict grammar takes the host path.
+
 Divergence note: with `schema=None` the column types come from Arrow C++'s CSV / JSON type inference, which is close to
 but not the same code as arrow-rs' `Format::infer_schema` (csv.rs:58); pass an explicit schema for exact control."""
 from __future__ import annotations
@@ -15,6 +18,7 @@ from typing import Optional, Sequence
 
 import pyarrow as pa
 
+from ._ffi import DeviceTable
 from .plan import MemoryTable
 
 
@@ -33,16 +37,100 @@ def _table_of(tbl: pa.Table, batch_rows: Optional[int]) -> MemoryTable:
     return MemoryTable(tbl.schema, batches, lazy_upload=True)
 
 
-def read_csv(path: str, options: Optional[CsvReadOptions] = None, schema: Optional[pa.Schema] = None,
-             batch_rows: Optional[int] = 1 << 20) -> MemoryTable:
-    """read_csv (datasource/file/csv.rs:33-70): the whole file becomes one in-memory table"""
+class DeviceCsvTable(MemoryTable):
+    """A CSV file decoded on the device (qhip_table_from_csv): `device_table()` IS the decoded table, nothing was parsed on
+    the host. `.data` — what the oracle, `insert` and `delete` work on — is downloaded the first time somebody asks for it;
+    from then on MemoryTable's rule holds (the device copy is kept for as long as `data` holds the very batches it stands for)."""
+
+    decoded_on_device = True
+
+    def __init__(self, schema: pa.Schema, device: DeviceTable):
+        self._schema = schema
+        self._data = None
+        self.lazy_upload = True
+        self._device = device
+        self._device_of = None
+
+    @property
+    def data(self):
+        if self._data is None:
+            self._data = self._device.to_batches()
+            self._device_of = tuple(self._data)
+        return self._data
+
+    @data.setter
+    def data(self, value):
+        self._data = value
+
+    def device_table(self) -> DeviceTable:
+        if self._data is None:
+            return self._device
+        return super().device_table()
+
+
+def _host_read_csv(path, o, schema, batch_rows, columns) -> MemoryTable:
     import pyarrow.csv as pacsv
-    o = options or CsvReadOptions()
     names = [f.name for f in schema] if (schema is not None and not o.has_header) else None
     read = pacsv.ReadOptions(autogenerate_column_names=(not o.has_header and names is None), column_names=names)
     parse = pacsv.ParseOptions(delimiter=o.delimiter, quote_char=o.quote if o.quote else '"', escape_char=o.escape if o.escape else False)
     conv = pacsv.ConvertOptions(column_types=schema) if schema is not None else pacsv.ConvertOptions()
+    if columns is not None:
+        conv.include_columns = list(columns)
     return _table_of(pacsv.read_csv(path, read_options=read, parse_options=parse, convert_options=conv), batch_rows)
+
+
+def _device_read_csv(path, o, schema, batch_rows, columns) -> Optional[MemoryTable]:
+    """the device path, or None when the file needs the host path (QHIP_UNSUPPORTED)"""
+    import mmap
+    import os
+    import pyarrow.csv as pacsv
+    from ._ffi import UnsupportedError, get_context
+    if schema is None:
+        # the types the host path would infer: Arrow C++ infers them from the first block it reads
+        read = pacsv.ReadOptions(autogenerate_column_names=not o.has_header)
+        parse = pacsv.ParseOptions(delimiter=o.delimiter, quote_char=o.quote if o.quote else '"', escape_char=o.escape if o.escape else False)
+        try:
+            with pacsv.open_csv(path, read_options=read, parse_options=parse) as rd:
+                schema = rd.schema
+        except pa.ArrowInvalid:
+            return None
+    schema = pa.schema([pa.field(f.name, f.type) for f in schema])   # as the host parse returns it: every field nullable, no metadata
+    idx = None
+    if columns is not None:
+        idx = [schema.get_field_index(c) for c in columns]
+        if any(k < 0 for k in idx):
+            return None
+    if os.path.getsize(path) == 0:
+        return None
+    with open(path, "rb") as f, mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ) as m:
+        try:
+            dev = DeviceTable.from_csv_bytes(get_context(), schema, m, has_header=o.has_header, delimiter=o.delimiter, quote=o.quote if o.quote else '"',
+                                             escape=o.escape, columns=idx, batch_rows=batch_rows)
+        except UnsupportedError:
+            return None
+    out_schema = schema if idx is None else pa.schema([schema.field(k) for k in idx])
+    return DeviceCsvTable(out_schema, dev)
+
+
+def read_csv(path: str, options: Optional[CsvReadOptions] = None, schema: Optional[pa.Schema] = None,
+             batch_rows: Optional[int] = 1 << 20, device: Optional[bool] = None, columns: Optional[Sequence[str]] = None) -> MemoryTable:
+    """read_csv (datasource/file/csv.rs:33-70): the whole file becomes one in-memory table. `columns`: the names of the
+    columns to read, in output order (None = all).
+
+    device=True (None: the environment's QHIP_CSV_DEVICE, default 0): the file's text is decoded on the device
+    (qhip_table_from_csv) and the result's `decoded_on_device` is True; a file outside the device's strict
+    grammar falls back silently to the host parse below, which also produces every error message."""
+    import os
+    o = options or CsvReadOptions()
+    if device is None:
+        device = os.environ.get("QHIP_CSV_DEVICE", "0") not in ("", "0")
+    if device:
+        t = _device_read_csv(path, o, schema, batch_rows, columns)
+        if t is not None:
+            return t
+    t = _host_read_csv(path, o, schema, batch_rows, columns)
+    t.decoded_on_device = False
+    return t
 
 
 def read_parquet(path: str, columns: Optional[Sequence[str]] = None, batch_rows: Optional[int] = 1 << 20) -> MemoryTable:

@@ -115,6 +115,16 @@ pub struct qhip_agg {
     pub return_type: qhip_dtype,
 }
 
+/// qhip_table_from_csv: how the file is split (quote / escape only decide whether the device may decode it at all)
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct qhip_csv_options {
+    pub has_header: i32,
+    pub delimiter: i32,
+    pub quote: i32,
+    pub escape: i32,
+}
+
 #[repr(C)]
 #[derive(Clone, Copy)]
 pub struct qhip_exec_stats {
@@ -203,6 +213,18 @@ extern "C" {
         n_batches: i64,
         out: *mut *mut qhip_table,
     ) -> c_int;
+    pub fn qhip_table_from_csv(
+        ctx: *mut qhip_ctx,
+        schema: *const FFI_ArrowSchema,
+        bytes: *const c_void,
+        n_bytes: i64,
+        options: *const qhip_csv_options,
+        columns: *const i32,
+        n_columns: i32,
+        batch_rows: i64,
+        out: *mut *mut qhip_table,
+    ) -> c_int;
+    pub fn qhip_ctx_csv_pass_ms(ctx: *const qhip_ctx, out: *mut f64, n_out: i32) -> c_int;
     pub fn qhip_table_to_arrow(
         ctx: *mut qhip_ctx,
         t: *const qhip_table,

@@ -1,0 +1,127 @@
+"""What getting a CSV table onto the device costs: about --gb GB of lineitem-shaped text (synth.lineitem written
+once with pyarrow.csv.write_csv, quoting_style="none", into a temporary directory), and per measurement the median of --runs
+calls after --warmup calls, each ending in a device synchronise:
+
+  (a) host path    datasource.read_csv(device=False) — Arrow C++ parse with --threads threads — plus the eager upload of the
+                   columns Q1 reads (all seven of this table)
+  (b) device path  datasource.read_csv(device=True) as a whole call: mmap, upload of the text, the kernels, both host waits
+  (c) floor        one plain host-to-device copy of the file's bytes out of the same mapping (hipMemcpy, pageable source)
+  (d) passes       HIP events around the device path's passes (timing on, calls of their own): upload, k_csv_scan, record starts
+                   (scan of the chunk counts + k_csv_scan<true>), k_csv_decode, Utf8 (offset scans + k_csv_copy_utf8), with the
+                   GB/s of file bytes each pass amounts to
+
+(a) .. (c) alternate in one process, --repeat times.
+
+    python tools/csv_decode_timing.py [--gb 1.0] [--runs 10] [--warmup 2] [--repeat 2] [--threads 16]
+"""
+import argparse
+import ctypes as C
+import mmap
+import os
+import statistics
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import pyarrow as pa  # noqa: E402
+import pyarrow.csv as pacsv  # noqa: E402
+
+import qurious_amd as q  # noqa: E402
+from qurious_amd import datasource, synth  # noqa: E402
+from qurious_amd._ffi import DeviceTable  # noqa: E402
+
+PASSES = ["upload", "k_csv_scan", "record starts", "k_csv_decode", "Utf8 offsets + k_csv_copy_utf8"]
+
+
+def write_file(path, target_bytes):
+    """lineitem rows until the file has about target_bytes; returns the row count"""
+    step, rows = 1 << 20, 0
+    with open(path, "wb") as f:
+        while f.tell() < target_bytes:
+            batch = synth.lineitem_batch(rows, step)
+            pacsv.write_csv(pa.Table.from_batches([batch]), f, write_options=pacsv.WriteOptions(include_header=rows == 0, quoting_style="none"))
+            rows += step
+    return rows
+
+
+def median_ms(fn, runs, warmup):
+    for _ in range(warmup):
+        fn()
+    out = []
+    for _ in range(runs):
+        t0 = time.perf_counter()
+        fn()
+        out.append((time.perf_counter() - t0) * 1e3)
+    return statistics.median(out), min(out)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--gb", type=float, default=1.0)
+    ap.add_argument("--runs", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--repeat", type=int, default=2)
+    ap.add_argument("--threads", type=int, default=16)
+    args = ap.parse_args()
+    pa.set_cpu_count(args.threads)
+    ctx = q.get_context()
+    schema = pa.schema([pa.field(f.name, f.type) for f in synth.LINEITEM_SCHEMA])
+    hip = C.CDLL(None)   # (libqhip.so is loaded globally and brings the HIP runtime with it)
+    hip.hipMalloc.argtypes, hip.hipMemcpy.argtypes, hip.hipFree.argtypes = [C.POINTER(C.c_void_p), C.c_size_t], [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int], [C.c_void_p]
+    with tempfile.TemporaryDirectory() as d:
+        path = os.path.join(d, "lineitem.csv")
+        rows = write_file(path, int(args.gb * 1e9))
+        nbytes = os.path.getsize(path)
+        print(f"device {ctx.device_name()}; {path}: {nbytes} bytes, {rows} rows, {nbytes / rows:.1f} bytes per record; median (min) of {args.runs} calls "
+              f"after {args.warmup} warm-up calls; host parse with {args.threads} threads", flush=True)
+
+        def host_path():
+            t = datasource.read_csv(path, schema=schema, device=False)
+            dev = DeviceTable.from_batches(ctx, t.schema(), t.data, lazy=False)
+            ctx.synchronize()
+            return dev
+
+        def device_path():
+            t = datasource.read_csv(path, schema=schema, device=True)
+            assert t.decoded_on_device
+            ctx.synchronize()
+            return t.device_table()
+
+        dst = C.c_void_p()
+        assert hip.hipMalloc(C.byref(dst), nbytes + 64) == 0
+        f = open(path, "rb")
+        m = mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ)
+        src = pa.py_buffer(m)
+
+        def floor():
+            assert hip.hipMemcpy(dst, C.c_void_p(src.address), nbytes, 1) == 0   # (hipMemcpyHostToDevice; returns when the copy is done)
+
+        assert host_path().num_rows == device_path().num_rows == rows
+        for rep in range(args.repeat):
+            for name, fn in (("(a) host parse + upload", host_path), ("(b) device path, whole call", device_path), ("(c) plain copy of the file", floor)):
+                med, low = median_ms(fn, args.runs, args.warmup)
+                print(f"run {rep + 1} {name:30s} {med:9.2f} ms (min {low:9.2f})  {nbytes / med / 1e6:8.2f} GB/s of file bytes", flush=True)
+        ctx.set_timing(True)
+        per = []
+        for _ in range(args.warmup + args.runs):
+            device_path()
+            per.append(ctx.csv_pass_ms())
+        ctx.set_timing(False)
+        per = per[args.warmup:]
+        kernels = 0.0
+        for k, name in enumerate(PASSES):
+            med = statistics.median(p[k] for p in per)
+            kernels += med if k else 0.0
+            print(f"(d) {name:32s} {med:9.3f} ms  {nbytes / max(med, 1e-6) / 1e6:9.1f} GB/s of file bytes", flush=True)
+        print(f"(d) kernels together (all but the upload) {kernels:9.3f} ms  {nbytes / max(kernels, 1e-6) / 1e6:9.1f} GB/s of file bytes", flush=True)
+        del src
+        m.close()
+        f.close()
+        hip.hipFree(dst)
+
+
+if __name__ == "__main__":
+    main()
