@@ -295,14 +295,23 @@ int qhip_table_from_arrow_lazy(qhip_ctx* ctx, const struct ArrowSchema* schema, 
  * projected is never parsed. batch_rows: a batch boundary every batch_rows rows (<= 0: one batch).
  * The call is eager and exact or not at all: QHIP_OK with a table whose columns are what qhip_table_from_arrow would hold after
  * a host parse of the same bytes (Arrow C++ with this schema), or QHIP_UNSUPPORTED with nothing created — the message names the
- * first reason and the record — and the caller takes the host path. Outside the device's grammar ("needs host"): any quote
- * byte, a '\r' without '\n', a byte order mark, an empty file, an empty line, a short or long record, a header that differs
- * from the schema's names, escape >= 0, a projected column that is not Int8..Int64, UInt8..UInt64, Float64, Date32,
- * Decimal128(p, s >= 0) or Utf8, and every field spelling outside the strict grammar of csrc/device/qhip_csv.inc. */
+ * first reason and the record — and the caller takes the host path.
+ * The grammar has two levels (qhip_ctx_set_csv_grammar below). Outside the device's grammar ("needs host") at BOTH levels: a
+ * '\r' without '\n', a byte order mark, an empty file, an empty line, a short or long record, a header that differs from the
+ * schema's names, escape >= 0, a Float32, Time, Decimal256 or zoned Timestamp column, and every field spelling outside the strict
+ * grammar of csrc/device/qhip_csv.inc (the lenient spellings Arrow accepts, and everything Arrow refuses).
+ * Level 1 (the default): any quote byte in the data needs the host; projected columns are Int8..Int64, UInt8..UInt64, Float64,
+ * Date32, Decimal128(p, s >= 0) or Utf8.
+ * Level 2 adds: fields in quotes — the first and last byte of the field are the quote and every quote in between is half of a
+ * doubled pair, which stands for one quote; a delimiter inside is data; "" is NULL in a non-Utf8 column and the empty string in a
+ * Utf8 column; any other use of the quote byte, in a projected field or not, needs the host, and so does a line end inside
+ * quotes (every '\n' ends a record) and a quote byte >= 0x80 — and the column types Boolean (exactly true / false) and
+ * Timestamp(s | ms | us | ns) without a zone (YYYY-MM-DD, ' ' or 'T', hh:mm:ss, then '.' and as many digits as the unit holds at
+ * the most). */
 typedef struct qhip_csv_options {
   int32_t has_header;   /* skip the first record (its names must equal the schema's) */
   int32_t delimiter;    /* one byte, e.g. ',' or '|' */
-  int32_t quote;        /* the byte that makes a file "not plain" (usually '"'); -1: none */
+  int32_t quote;        /* the quote byte (usually '"'): level 1, a file that holds it needs the host; level 2, fields may stand in it; -1: none */
   int32_t escape;       /* -1: none; anything else -> QHIP_UNSUPPORTED */
 } qhip_csv_options;
 int qhip_table_from_csv(qhip_ctx* ctx, const struct ArrowSchema* schema, const void* bytes, int64_t n_bytes,
@@ -311,6 +320,10 @@ int qhip_table_from_csv(qhip_ctx* ctx, const struct ArrowSchema* schema, const v
 /* Device time (ms) of the last qhip_table_from_csv's five passes — upload, scan, record starts, decode, Utf8 — when the
  * context's timing is on (qhip_ctx_set_timing); zeros otherwise. n_out must be 5. */
 int qhip_ctx_csv_pass_ms(const qhip_ctx* ctx, double* out, int32_t n_out);
+/* The grammar qhip_table_from_csv decodes. level 1 (the default): plain fields only. level 2: also canonical quoted fields and
+ * Boolean / Timestamp columns, decoded by kernels of their own — level 1 launches what it always launched. The environment's
+ * QHIP_CSV_GRAMMAR (1 / 2) is read when the context is created. */
+int qhip_ctx_set_csv_grammar(qhip_ctx* ctx, int32_t level);
 /* Download batch `batch_index` as a struct ArrowArray (+ schema if out_schema != NULL).
  * Buffers are library-owned host memory freed by the release callbacks.
  * batch_index == -1: every row of the table as ONE array — a caller facing thousands of small batches (the reference's

@@ -43,6 +43,8 @@ class Context {
   // hash join keys that do not fit the packed key words are encoded to shared key codes first (qhip.h: 0 off, 1 when needed, 2 always)
   void set_wide_join_keys(int mode) const { check(qhip_ctx_set_wide_join_keys(ctx_, mode)); }
   int64_t wide_key_joins() const { return qhip_ctx_wide_key_joins(ctx_); }
+  // the device CSV decoder's grammar (qhip.h: 1 plain fields only, 2 also quoted fields, Boolean and Timestamp columns)
+  void set_csv_grammar(int level) const { check(qhip_ctx_set_csv_grammar(ctx_, level)); }
 
  private:
   qhip_ctx* ctx_ = nullptr;

@@ -141,6 +141,7 @@ def load_library() -> C.CDLL:
             "qhip_ctx_set_wide_group_keys": (C.c_int, [vp, i32]),
             "qhip_ctx_wide_key_aggregates": (i64, [vp]),
             "qhip_ctx_set_wide_join_keys": (C.c_int, [vp, i32]),
+            "qhip_ctx_set_csv_grammar": (C.c_int, [vp, i32]),
             "qhip_ctx_wide_key_joins": (i64, [vp]),
             "qhip_ctx_allow_deferred_sizes": (C.c_int, [vp, i32]),
             "qhip_ctx_forget_plans": (C.c_int, [vp]),
@@ -262,6 +263,11 @@ class Context:
     def wide_key_joins(self) -> int:
         """Hash join calls of this context that went through the wide-key encoding stage so far."""
         return int(self.lib.qhip_ctx_wide_key_joins(self.handle))
+
+    def set_csv_grammar(self, level: int):
+        """The device CSV decoder's grammar: 1 (the default) plain fields only, any quote byte needs the host; 2 also canonical
+        quoted fields, Boolean and Timestamp columns. QHIP_CSV_GRAMMAR sets it when the context is made."""
+        self.check(self.lib.qhip_ctx_set_csv_grammar(self.handle, int(level)))
 
     def csv_pass_ms(self) -> List[float]:
         """Device time (ms) of the last device CSV decode's passes: upload, scan, record starts, decode, Utf8 (timing on)."""

@@ -283,6 +283,9 @@ struct Ctx {
   float wide_join_stage_ms = 0;
   // device time of the last qhip_table_from_csv's passes (csv.cpp; timing on): upload, scan, record starts, decode, Utf8
   float csv_pass_ms[5] = {0, 0, 0, 0, 0};
+  // the device CSV decoder's grammar level (csv.cpp): 1 = plain fields only, 2 = + canonical quoted fields, Boolean, Timestamp;
+  // QHIP_CSV_GRAMMAR at context creation, qhip_ctx_set_csv_grammar later
+  int csv_grammar = 1;
   // (total_out: the output table's own host word — the page-locked slot is part of a ring and is reused by later joins, so
   // the verified total is copied where the table can still find it however long it stays unsettled)
   struct PendingSize { uint32_t* slot; uint64_t key; uint64_t capacity; uint64_t dup_hint; std::shared_ptr<uint64_t> total_out; };

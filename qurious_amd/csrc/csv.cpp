@@ -4,7 +4,9 @@
 // upload). Here the text itself crosses PCIe once and is decoded where the columns will live; columns that are not projected
 // are never parsed. The decoder knows only a strict canonical grammar (device/qhip_csv.inc): whatever lies outside it makes
 // the whole call answer QHIP_UNSUPPORTED with nothing created, and the caller takes the host path, which then produces the
-// lenient spellings and the error messages itself.
+// lenient spellings and the error messages itself. The grammar has two levels (qhip_ctx_set_csv_grammar): 1, the default, knows
+// no quotes; 2 adds canonical quoted fields, Boolean and Timestamp columns through instantiations of their own of the decode and
+// copy kernels, so that level 1 launches exactly what it launched before.
 //
 // Passes, all on the context's stream:
 //   1 upload           the file into one contiguous device buffer (plain asynchronous copies, 64 MB each)
@@ -27,8 +29,11 @@ static std::string needs_host(unsigned reason, uint64_t record) {
   return std::string("CSV needs the host path: ") + qh_csv_reason_text(reason) + " in record " + std::to_string(record);
 }
 
-static bool csv_decodable(const DType& t) {
+static bool is_timestamp(const DType& t) { return t.id >= QHIP_TIMESTAMP_S && t.id <= QHIP_TIMESTAMP_NS; }
+
+static bool csv_decodable(const DType& t, int grammar) {
   if (dtype_is_integer(t)) return true;
+  if (grammar >= 2 && (t.id == QHIP_BOOL || is_timestamp(t))) return true;   // (a zoned Timestamp never gets here: dtype_from_format refuses it)
   if (t.id == QHIP_DECIMAL128) return t.scale >= 0 && t.precision >= 1 && t.precision <= 38 && t.scale <= 38;
   return t.id == QHIP_FLOAT64 || t.id == QHIP_DATE32 || t.id == QHIP_UTF8;
 }
@@ -47,6 +52,10 @@ qhip_table* table_from_csv(Ctx* ctx, const ArrowSchema* schema, const uint8_t* b
   if (opt.escape >= 0) fail(QHIP_UNSUPPORTED, "CSV needs the host path: an escape character is set");
   if (opt.quote > 255) fail(QHIP_INVALID_ARGUMENT, "qhip_table_from_csv: the quote must be one byte or -1");
   const int quote = opt.quote < 0 ? -1 : opt.quote;
+  // grammar level 2: canonical quoted fields are decoded, so the quote byte is no structural reason any more. The byte must be
+  // ASCII (dropping one of a doubled pair then leaves a value's UTF-8 validity as it is)
+  const int grammar = ctx->csv_grammar;
+  if (grammar >= 2 && quote >= 0x80) fail(QHIP_UNSUPPORTED, "CSV needs the host path: the quote is not an ASCII byte");
 
   // ---- the projection: types are checked before anything is uploaded
   std::vector<int32_t> proj;
@@ -57,7 +66,7 @@ qhip_table* table_from_csv(Ctx* ctx, const ArrowSchema* schema, const uint8_t* b
   for (int32_t c : proj) {
     if (c < 0 || c >= nfields) fail(QHIP_INVALID_ARGUMENT, "qhip_table_from_csv: projected column " + std::to_string(c) + " is not in the schema");
     const DType t = dtype_from_format(schema->children[c]->format);   // (unknown formats: QHIP_UNSUPPORTED)
-    if (!csv_decodable(t)) fail(QHIP_UNSUPPORTED, "CSV needs the host path: column type " + dtype_name(t) + " is not decoded on the device");
+    if (!csv_decodable(t, grammar)) fail(QHIP_UNSUPPORTED, "CSV needs the host path: column type " + dtype_name(t) + " is not decoded on the device");
     types.push_back(t);
   }
 
@@ -132,7 +141,9 @@ qhip_table* table_from_csv(Ctx* ctx, const ArrowSchema* schema, const uint8_t* b
     // ---- 2. record ends
     const uint64_t nchunks = (n + kCsvChunk - 1) / kCsvChunk;
     DevBuf counts((size_t)(nchunks + 1) * 4);
-    launch_csv_scan(file.as<uint8_t>(), d0, n, quote, counts.as<uint32_t>(), st_dev, st_dev + 1, ctx->stream);
+    // (level 2: every '\n' still ends a record, a quote is no reason here; a line end inside quotes shows in the decode as a
+    // record with an unterminated quote)
+    launch_csv_scan(file.as<uint8_t>(), d0, n, grammar >= 2 ? -1 : quote, counts.as<uint32_t>(), st_dev, st_dev + 1, ctx->stream);
     mark(2);
     std::vector<uint64_t> back(st_host.size());
     copy_sync(ctx->stream, back.data(), st.ptr, 16, hipMemcpyDeviceToHost);   // host wait 1 (also: the upload has left `bytes`)
@@ -171,6 +182,9 @@ qhip_table* table_from_csv(Ctx* ctx, const ArrowSchema* schema, const uint8_t* b
         o.strpos = std::make_shared<DevBuf>((size_t)R * 8);
         d.kind = QH_CSV_K_UTF8; d.width = 4;
         d.strpos = o.strpos->as<uint64_t>();
+      } else if (ty.id == QHIP_BOOL) {
+        o.col.values = std::make_shared<DevBuf>((size_t)((R + 63) / 64) * 8);   // bit-packed; the kernel writes whole 64-row words
+        d.kind = QH_CSV_K_BOOL;
       } else {
         const int w = dtype_width(ty);
         o.col.values = std::make_shared<DevBuf>((size_t)R * (size_t)w);
@@ -178,13 +192,18 @@ qhip_table* table_from_csv(Ctx* ctx, const ArrowSchema* schema, const uint8_t* b
         if (dtype_is_integer(ty)) { d.kind = QH_CSV_K_INT; d.a = dtype_is_signed(ty) ? 1 : 0; }
         else if (ty.id == QHIP_DATE32) d.kind = QH_CSV_K_DATE32;
         else if (ty.id == QHIP_FLOAT64) d.kind = QH_CSV_K_FLOAT64;
+        else if (is_timestamp(ty)) { d.kind = QH_CSV_K_TIMESTAMP; d.a = (uint8_t)(3 * (ty.id - QHIP_TIMESTAMP_S)); }
         else { d.kind = QH_CSV_K_DECIMAL128; d.a = (uint8_t)ty.precision; d.b = (uint8_t)ty.scale; }
       }
       d.values = o.col.values->ptr;
     }
     time_mark(ctx, 2);
-    launch_csv_decode(file.as<uint8_t>(), n, starts.as<uint64_t>(), R, desc, (int)order.size(), (uint32_t)nfields, opt.delimiter, st_dev, st_dev + 2,
-                      st_dev + 2 + kCsvCols, ctx->stream);
+    if (grammar >= 2)
+      launch_csv_decode_q(file.as<uint8_t>(), n, starts.as<uint64_t>(), R, desc, (int)order.size(), (uint32_t)nfields, opt.delimiter, quote, st_dev, st_dev + 2,
+                          st_dev + 2 + kCsvCols, ctx->stream);
+    else
+      launch_csv_decode(file.as<uint8_t>(), n, starts.as<uint64_t>(), R, desc, (int)order.size(), (uint32_t)nfields, opt.delimiter, st_dev, st_dev + 2,
+                        st_dev + 2 + kCsvCols, ctx->stream);
     time_mark(ctx, 3);
     mark(4);
     copy_sync(ctx->stream, back.data(), st.ptr, st.bytes, hipMemcpyDeviceToHost);   // host wait 2
@@ -201,7 +220,8 @@ qhip_table* table_from_csv(Ctx* ctx, const ArrowSchema* schema, const uint8_t* b
       o.col.data_bytes = (int64_t)total;
       uint32_t* off = o.col.values->as<uint32_t>();
       exclusive_scan_u32(off, off, R, off + R, ctx->stream);
-      launch_csv_copy_utf8(file.as<uint8_t>(), o.strpos->as<uint64_t>(), off, R, o.col.data->as<uint8_t>(), ctx->stream);
+      if (grammar >= 2 && quote >= 0) launch_csv_copy_utf8_q(file.as<uint8_t>(), o.strpos->as<uint64_t>(), off, R, o.col.data->as<uint8_t>(), quote, ctx->stream);
+      else launch_csv_copy_utf8(file.as<uint8_t>(), o.strpos->as<uint64_t>(), off, R, o.col.data->as<uint8_t>(), ctx->stream);
     }
     mark(5);
     for (auto& o : outs) t->cols.push_back(std::move(o.col));

@@ -27,7 +27,11 @@
 #define QH_CSV_R_FLOAT 9
 #define QH_CSV_R_UTF8 10         // invalid UTF-8
 #define QH_CSV_R_UTF8_LONG 11    // one Utf8 field of more than 2^31 - 1 bytes
-#define QH_CSV_R_COUNT 12
+// (grammar level 2 only, qhip_ctx_set_csv_grammar)
+#define QH_CSV_R_QUOTING 12      // a field that holds the quote byte and is not a canonical quoted field
+#define QH_CSV_R_BOOL 13
+#define QH_CSV_R_TIMESTAMP 14
+#define QH_CSV_R_COUNT 15
 
 QH_CSV_HD inline const char* qh_csv_reason_text(unsigned r) {
   switch (r) {
@@ -41,6 +45,9 @@ QH_CSV_HD inline const char* qh_csv_reason_text(unsigned r) {
     case QH_CSV_R_FLOAT: return "a float outside the exactly convertible spellings";
     case QH_CSV_R_UTF8: return "invalid UTF-8";
     case QH_CSV_R_UTF8_LONG: return "a string field of 2 GiB or more";
+    case QH_CSV_R_QUOTING: return "quoting outside the canonical form";
+    case QH_CSV_R_BOOL: return "a boolean that is not true or false";
+    case QH_CSV_R_TIMESTAMP: return "a timestamp outside YYYY-MM-DD[ T]hh:mm:ss[.fraction] or outside its unit's range";
     default: return "an unknown reason";
   }
 }
@@ -59,13 +66,15 @@ QH_CSV_HD inline unsigned qh_csv_byte_class(unsigned char b, int quote) {
 #define QH_CSV_K_DECIMAL128 2
 #define QH_CSV_K_FLOAT64 3
 #define QH_CSV_K_UTF8 4
+#define QH_CSV_K_BOOL 5          // grammar level 2: no `values` store per row, the kernel packs 64 rows into one ballot word
+#define QH_CSV_K_TIMESTAMP 6     // grammar level 2: a = fraction digits of the unit (0 s, 3 ms, 6 us, 9 ns)
 struct qh_csv_col {
   void* values;                  // row-indexed values of `width` bytes; Utf8: the u32 LENGTH of every row (scanned into offsets later)
   unsigned long long* valid;     // one ballot word per 64 rows (written by the kernel, not by the functions below)
   unsigned long long* strpos;    // Utf8: where the field starts in the file (64-bit: files are larger than 4 GB)
   unsigned field;                // index of the field inside a record
   unsigned char kind, width;     // QH_CSV_K_*; bytes per value (Int: 1, 2, 4, 8)
-  unsigned char a, b;            // Int: a = signed; Decimal128: a = precision, b = scale
+  unsigned char a, b;            // Int: a = signed; Decimal128: a = precision, b = scale; Timestamp: a = fraction digits
 };
 
 // ---- integers: -?[0-9]+ inside the type's range (leading zeros are fine, "-0" is 0, no '-' at all for unsigned types)
@@ -322,4 +331,186 @@ QH_CSV_HD inline int qh_csv_decode_record(const qh_csv_col* cols, int ncols, uns
   *valid_mask = vm;
   if (f != nfields) return QH_CSV_R_FIELD_COUNT;
   return reason;
+}
+
+// ================================================================ grammar level 2 (qhip_ctx_set_csv_grammar; DESIGN §3.8)
+// Quoted fields, Boolean and Timestamp columns. Everything above is level 1 and stays as it is: the level-1 kernel calls
+// qh_csv_decode_record, the level-2 kernel calls qh_csv_decode_record_q below.
+
+// ---- Boolean: exactly "true" or "false"
+QH_CSV_HD inline int qh_csv_parse_bool(const unsigned char* p, unsigned long long len, int* out) {
+  if (len == 0) return QH_CSV_NULL;
+  if (len == 4 && p[0] == 't' && p[1] == 'r' && p[2] == 'u' && p[3] == 'e') { *out = 1; return QH_CSV_OK; }
+  if (len == 5 && p[0] == 'f' && p[1] == 'a' && p[2] == 'l' && p[3] == 's' && p[4] == 'e') { *out = 0; return QH_CSV_OK; }
+  return QH_CSV_R_BOOL;
+}
+
+// ---- Timestamp without a zone: YYYY-MM-DD, one ' ' or 'T', hh:mm:ss, then optionally '.' and 1..digits digits (digits: 0 for
+// seconds, 3, 6, 9), padded on the right -> units since 1970-01-01T00:00:00. Nanoseconds must fit 64 bits.
+QH_CSV_HD inline int qh_csv_parse_timestamp(const unsigned char* p, unsigned long long len, int digits, long long* out) {
+  if (len == 0) return QH_CSV_NULL;
+  if (len < 19 || len > 20ULL + (unsigned)digits || len == 20) return QH_CSV_R_TIMESTAMP;
+  if ((p[10] != ' ' && p[10] != 'T') || p[13] != ':' || p[16] != ':') return QH_CSV_R_TIMESTAMP;
+  int days = 0;
+  if (qh_csv_parse_date32(p, 10, &days) != QH_CSV_OK) return QH_CSV_R_TIMESTAMP;
+  unsigned t[3];
+  for (int k = 0; k < 3; ++k) {
+    const unsigned hi = (unsigned)p[11 + 3 * k] - (unsigned)'0', lo = (unsigned)p[12 + 3 * k] - (unsigned)'0';
+    if (hi > 9u || lo > 9u) return QH_CSV_R_TIMESTAMP;
+    t[k] = hi * 10u + lo;
+  }
+  if (t[0] > 23u || t[1] > 59u || t[2] > 59u) return QH_CSV_R_TIMESTAMP;
+  unsigned long long frac = 0;
+  if (len > 19) {
+    if (p[19] != '.') return QH_CSV_R_TIMESTAMP;
+    for (unsigned long long i = 20; i < len; ++i) {
+      const unsigned d = (unsigned)p[i] - (unsigned)'0';
+      if (d > 9u) return QH_CSV_R_TIMESTAMP;
+      frac = frac * 10ULL + d;
+    }
+    for (unsigned long long i = len; i < 20ULL + (unsigned)digits; ++i) frac *= 10ULL;
+  }
+  const long long secs = (long long)days * 86400LL + (long long)(t[0] * 3600u + t[1] * 60u + t[2]);
+  unsigned long long mul = 1;
+  for (int k = 0; k < digits; ++k) mul *= 10ULL;
+  if (digits == 9) {
+    // 1677-09-21T00:12:44 to 2262-04-11T23:47:16.854775807. Arrow C++ refuses every instant whose whole seconds alone do not
+    // fit as nanoseconds, so the 0.854775808 s below -9223372036 s that int64 could hold belong to the host and its error
+    if (secs > 9223372036LL || (secs == 9223372036LL && frac > 854775807ULL)) return QH_CSV_R_TIMESTAMP;
+    if (secs < -9223372036LL) return QH_CSV_R_TIMESTAMP;
+  }
+  *out = (long long)((unsigned long long)secs * mul + frac);   // (unsigned arithmetic: a negative count of seconds wraps as two's complement does)
+  return QH_CSV_OK;
+}
+
+// ---- Utf8 at level 2: bits 63 and 62 of strpos[row]. Positions in a file stay far below 2^62.
+#define QH_CSV_POS_PAIRS (1ULL << 63)   // the field holds doubled quotes: the copy drops the second of every pair
+#define QH_CSV_POS_LONG (1ULL << 62)    // ... and its raw inner span is longer than 64 bytes: the whole wavefront copies it
+#define QH_CSV_POS_MASK ((1ULL << 62) - 1ULL)
+
+// the reason a column's kind gives when its field cannot be a value of it
+QH_CSV_HD inline int qh_csv_kind_reason(int kind) {
+  switch (kind) {
+    case QH_CSV_K_INT: return QH_CSV_R_INT;
+    case QH_CSV_K_DATE32: return QH_CSV_R_DATE;
+    case QH_CSV_K_DECIMAL128: return QH_CSV_R_DECIMAL;
+    case QH_CSV_K_FLOAT64: return QH_CSV_R_FLOAT;
+    case QH_CSV_K_BOOL: return QH_CSV_R_BOOL;
+    case QH_CSV_K_TIMESTAMP: return QH_CSV_R_TIMESTAMP;
+    default: return QH_CSV_R_UTF8;
+  }
+}
+
+// ---- one field of one row at level 2. [p, p + len): the field without its quotes, `pairs` doubled quotes still inside;
+// `filepos`: where p[0] is in the file. *truth: a Boolean's value (the kernel packs it; nothing is stored here).
+QH_CSV_HD inline int qh_csv_parse_store_q(const qh_csv_col& c, const unsigned char* p, unsigned long long len, unsigned long long pairs,
+                                          unsigned long long row, unsigned long long filepos, int* truth) {
+  switch (c.kind) {
+    case QH_CSV_K_UTF8: {
+      const unsigned long long ulen = len - pairs;   // the unescaped length: what the offsets and byte totals are made of
+      const bool too_long = ulen > 0x7fffffffULL;
+      ((unsigned*)c.values)[row] = too_long ? 0u : (unsigned)ulen;
+      c.strpos[row] = filepos | (pairs ? QH_CSV_POS_PAIRS | (len > 64 ? QH_CSV_POS_LONG : 0ULL) : 0ULL);
+      if (too_long) return QH_CSV_R_UTF8_LONG;
+      return qh_csv_check_utf8(p, len);   // (the quote is an ASCII byte: dropping one of two leaves validity as it is)
+    }
+    case QH_CSV_K_BOOL: {
+      int v = 0;
+      const int st = pairs ? QH_CSV_R_BOOL : qh_csv_parse_bool(p, len, &v);
+      *truth = st == QH_CSV_OK ? v : 0;
+      return st;
+    }
+    case QH_CSV_K_TIMESTAMP: {
+      long long v = 0;
+      const int st = pairs ? QH_CSV_R_TIMESTAMP : qh_csv_parse_timestamp(p, len, c.a, &v);
+      ((long long*)c.values)[row] = st == QH_CSV_OK ? v : 0;
+      return st;
+    }
+    default:
+      // a quote inside a number: no spelling of the strict grammar; the parser sees the raw bytes, so it is not asked
+      if (pairs) { qh_csv_parse_store(c, p, 0, row, filepos); return qh_csv_kind_reason(c.kind); }
+      return qh_csv_parse_store(c, p, len, row, filepos);
+  }
+}
+
+// ---- one record at level 2: as qh_csv_decode_record, with fields that may stand in quotes. A field is canonical when it
+// holds no quote byte, or begins and ends with one and every quote in between is half of a doubled pair; anything else is
+// QH_CSV_R_QUOTING, in projected and unprojected fields alike (where the next field begins depends on it), and ends the walk.
+// One state bit (`open`): a delimiter inside quotes is data. A record that the splitter cut at a line end inside a quoted
+// field ends with the bit still set: an unterminated quote, QH_CSV_R_QUOTING. quote < 0: no byte is a quote.
+// bit k of *true_mask: descriptor k is a Boolean column and the row's value is true.
+QH_CSV_HD inline int qh_csv_decode_record_q(const qh_csv_col* cols, int ncols, unsigned nfields, unsigned char delim, int quote, const unsigned char* p,
+                                            unsigned long long len, unsigned long long row, unsigned long long filepos,
+                                            unsigned long long* valid_mask, unsigned long long* true_mask) {
+  unsigned long long vm = 0, tm = 0;
+  int reason = QH_CSV_OK;
+  unsigned f = 0;
+  int k = 0;
+  unsigned long long a = 0;
+  *valid_mask = 0;
+  *true_mask = 0;
+  for (;;) {
+    unsigned long long b = a, va = a, vb, pairs = 0;
+    if (a < len && (int)p[a] == quote) {
+      bool open = true;
+      b = a + 1;
+      while (b < len) {
+        if ((int)p[b] == quote) {
+          if (b + 1 < len && (int)p[b + 1] == quote) { ++pairs; b += 2; continue; }
+          open = false;
+          break;
+        }
+        ++b;
+      }
+      if (open) return QH_CSV_R_QUOTING;                       // no closing quote
+      va = a + 1; vb = b;
+      ++b;
+      if (b < len && p[b] != delim) return QH_CSV_R_QUOTING;   // bytes behind the closing quote
+    } else {
+      bool seen = false;
+      while (b < len && p[b] != delim) { seen |= (int)p[b] == quote; ++b; }
+      if (seen) return QH_CSV_R_QUOTING;                       // a quote inside a field that does not begin with one
+      vb = b;
+    }
+    while (k < ncols && cols[k].field == f) {
+      int truth = 0;
+      const int st = qh_csv_parse_store_q(cols[k], p + va, vb - va, pairs, row, filepos + va, &truth);
+      if (st == QH_CSV_OK) { vm |= 1ULL << k; if (truth) tm |= 1ULL << k; }
+      else if (st != QH_CSV_NULL && reason == QH_CSV_OK) reason = st;
+      ++k;
+    }
+    ++f;
+    if (b >= len) break;
+    a = b + 1;
+    if (f > nfields) break;
+  }
+  *valid_mask = vm;
+  *true_mask = tm;
+  if (f != nfields) return QH_CSV_R_FIELD_COUNT;
+  return reason;
+}
+
+// ---- the undoubling copy's lane logic (k_csv_copy_utf8 at level 2). The wavefront takes a field's raw inner bytes 64 at a
+// time; `quotes` is the ballot of "my byte is the quote". Quotes come in runs: inside a run the bytes at odd distance from
+// its beginning are the second halves of pairs and are dropped. A run may cross the 64-byte steps: `carry` is how many
+// quotes (mod 2) of the run that reaches into this step stand in earlier steps (0 when the previous step's last byte was
+// no quote, and at the field's beginning).
+QH_CSV_HD inline bool qh_csv_undouble_drops(unsigned long long quotes, unsigned carry, int lane) {
+  if (!((quotes >> lane) & 1ULL)) return false;
+  const unsigned long long below = ~quotes & ((1ULL << lane) - 1ULL);   // the bytes below mine that are no quotes
+  unsigned dist;                                                          // my distance from the run's beginning
+  if (below == 0) dist = (unsigned)lane + carry;
+  else dist = (unsigned)lane - (unsigned)(64 - __builtin_clzll(below));
+  return (dist & 1u) != 0;
+}
+// the carry for the next step
+QH_CSV_HD inline unsigned qh_csv_undouble_carry(unsigned long long quotes, unsigned carry) {
+  if (!(quotes >> 63)) return 0u;
+  if (~quotes == 0ULL) return carry;                 // 64 quotes: an even number more
+  return (unsigned)__builtin_clzll(~quotes) & 1u;    // the run at the top began inside this step
+}
+// where a lane that keeps its byte writes it, counted from the field's first output byte: `emitted` bytes left the earlier
+// steps, `dropped` is the ballot of qh_csv_undouble_drops over this step
+QH_CSV_HD inline unsigned long long qh_csv_undouble_out(unsigned long long emitted, unsigned long long dropped, int lane) {
+  return emitted + (unsigned long long)__builtin_popcountll(~dropped & ((1ULL << lane) - 1ULL));
 }

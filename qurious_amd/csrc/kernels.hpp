@@ -158,4 +158,9 @@ void launch_csv_starts(const uint8_t* buf, uint64_t d0, uint64_t n, const uint32
 void launch_csv_decode(const uint8_t* buf, uint64_t n, const uint64_t* starts, uint64_t nrec, const CsvCols& cols, int ncols, uint32_t nfields, int delim,
                        uint64_t* err, uint64_t* null_counts, uint64_t* utf8_bytes, hipStream_t s);
 void launch_csv_copy_utf8(const uint8_t* buf, const uint64_t* strpos, const uint32_t* offsets, uint64_t nrows, uint8_t* data, hipStream_t s);
+// grammar level 2 (qhip_ctx_set_csv_grammar): the quote-aware decode (quote < 0: no byte is a quote; a Boolean column's `values` are
+// ballot words, 8 bytes per 64 rows) and the copy that undoubles the quotes of the rows whose strpos carries QH_CSV_POS_PAIRS
+void launch_csv_decode_q(const uint8_t* buf, uint64_t n, const uint64_t* starts, uint64_t nrec, const CsvCols& cols, int ncols, uint32_t nfields, int delim,
+                         int quote, uint64_t* err, uint64_t* null_counts, uint64_t* utf8_bytes, hipStream_t s);
+void launch_csv_copy_utf8_q(const uint8_t* buf, const uint64_t* strpos, const uint32_t* offsets, uint64_t nrows, uint8_t* data, int quote, hipStream_t s);
 }  // namespace qhip

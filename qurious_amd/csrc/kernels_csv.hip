@@ -4,8 +4,10 @@
 //
 //   k_csv_scan<false>  every byte once, 16 per lane and load: record ends per 16 KB chunk, structural needs-host reasons
 //   k_csv_scan<true>   the same walk again with the scanned chunk counts: where every record starts (u64)
-//   k_csv_decode       one record per lane, 256 consecutive records per workgroup, their bytes staged in LDS
+//   k_csv_decode<G>    one record per lane, 256 consecutive records per workgroup, their bytes staged in LDS (G = 1: the plain
+//                      walk; G = 2: quoted fields, Boolean, Timestamp)
 //   k_csv_copy_utf8    string bytes from the file into the column's data buffer, at the scanned offsets
+//   k_csv_copy_utf8_q  ... with doubled quotes undoubled (grammar level 2)
 //
 // Every byte offset into the file is 64 bits wide. Vector loads may read up to 15 bytes past the file's end: every device
 // allocation carries 64 bytes of slack (DevBuf::alloc), and what is read there is masked out before it is looked at.
@@ -148,7 +150,11 @@ __global__ __launch_bounds__(QH_BLOCK) void k_csv_scan(const u8* __restrict__ bu
 // coalesced 16-byte loads and every lane walks its record there (walking global memory byte by byte, 64 lanes touch 64 different
 // lines per load). A range that does not fit (one very long field) is walked in global memory instead. The parsers take
 // generic pointers, so both paths run the same code.
+// GRAMMAR = 1: the plain walk (qh_csv_decode_record). GRAMMAR = 2 (qhip_ctx_set_csv_grammar): the quote-aware walk, an
+// instantiation of its own so that the plain one carries nothing of it; the quote byte travels in bits 8.. of `delim` as
+// quote + 1 (0: no byte is a quote), and a Boolean column's values word of 64 rows is a ballot like its validity word.
 constexpr u32 kCsvLdsBytes = 48 * 1024;
+template <int GRAMMAR>
 __global__ __launch_bounds__(QH_BLOCK) void k_csv_decode(const u8* __restrict__ buf, u64 n, const u64* __restrict__ starts, u64 nrec, CsvColsArg cols,
                                                          int ncols, u32 nfields, u32 delim, u64* err, u64* null_counts, u64* utf8_bytes) {
   __shared__ __attribute__((aligned(16))) u8 tile[kCsvLdsBytes];
@@ -167,19 +173,27 @@ __global__ __launch_bounds__(QH_BLOCK) void k_csv_decode(const u8* __restrict__ 
   __syncthreads();
   const u64 row = r0 + threadIdx.x;
   const bool active = row < nrec;
-  u64 vm = 0;
+  u64 vm = 0, tm = 0;
   if (active) {
     const u64 s = starts[row];
     u64 len = starts[row + 1] - 1 - s;          // without the '\n'
     const u8* p = staged ? tile + (s - base) : buf + s;
     if (len > 0 && p[len - 1] == '\r') --len;   // ... and without the '\r' of a "\r\n"
-    const int reason = qh_csv_decode_record(cols.c, ncols, nfields, (u8)delim, p, len, row, s, &vm);
+    int reason;
+    if constexpr (GRAMMAR == 1) reason = qh_csv_decode_record(cols.c, ncols, nfields, (u8)delim, p, len, row, s, &vm);
+    else reason = qh_csv_decode_record_q(cols.c, ncols, nfields, (u8)delim, (int)(delim >> 8) - 1, p, len, row, s, &vm, &tm);
     if (reason != QH_CSV_OK) csv_report(err, row, (u32)reason);
   }
   const u64 live = qh_ballot(active);
   const int lane = qh_lane();
   for (int k = 0; k < ncols; ++k) {
     const u64 word = qh_ballot(active && ((vm >> k) & 1ULL));
+    if constexpr (GRAMMAR == 2) {
+      if (cols.c[k].kind == QH_CSV_K_BOOL) {
+        const u64 truth = qh_ballot(active && ((tm >> k) & 1ULL));   // (a NULL row's bit is 0)
+        if (lane == 0 && live) ((u64*)cols.c[k].values)[row >> 6] = truth;
+      }
+    }
     u64 bytes = 0;
     if (cols.c[k].kind == QH_CSV_K_UTF8) bytes = qh_wave_sum_u64(active ? (u64)((const u32*)cols.c[k].values)[row] : 0ULL);
     if (lane == 0 && live) {
@@ -216,6 +230,66 @@ __global__ __launch_bounds__(QH_BLOCK) void k_csv_copy_utf8(const u8* __restrict
   }
 }
 
+// The same at grammar level 2: strpos carries QH_CSV_POS_PAIRS for a row whose field holds doubled quotes (len is the
+// UNESCAPED length; the raw span is longer by one byte per pair). Rows without the mark are copied exactly as above. A marked
+// row of up to 64 raw bytes is undoubled by its own lane; a longer one (QH_CSV_POS_LONG) by the whole wavefront, 64 raw bytes
+// per step: the ballot of "my byte is the quote" tells every lane whether its byte is the dropped half of a pair and where
+// the bytes below it go (qh_csv_undouble_*: runs of quotes cross the steps, their parity is carried). The last step may read
+// up to 63 bytes behind the field's closing quote: inside the file or the slack behind its allocation, and never written
+// (their output position is at or behind the row's end).
+__global__ __launch_bounds__(QH_BLOCK) void k_csv_copy_utf8_q(const u8* __restrict__ buf, const u64* __restrict__ strpos, const u32* __restrict__ off, u64 nrows,
+                                                              u8* __restrict__ data, u32 quote) {
+  const u64 nwords = (nrows + 63) / 64;
+  const u64 wave_global = ((u64)blockIdx.x * QH_BLOCK + threadIdx.x) >> 6;
+  const u64 nwaves = ((u64)gridDim.x * QH_BLOCK) >> 6;
+  const int lane = qh_lane();
+  for (u64 j = wave_global; j < nwords; j += nwaves) {
+    const u64 k = j * 64 + lane;
+    u64 src = 0;
+    u32 dst = 0, len = 0;
+    if (k < nrows) { src = strpos[k]; dst = off[k]; len = off[k + 1] - dst; }
+    const bool pairs = (src & QH_CSV_POS_PAIRS) != 0, wide = (src & QH_CSV_POS_LONG) != 0;
+    src &= QH_CSV_POS_MASK;
+    if (!pairs) {
+      if (len <= 64) for (u32 b = 0; b < len; ++b) data[dst + b] = buf[src + b];
+    } else if (!wide) {
+      u64 q = src;   // (at most 64 raw bytes)
+      for (u32 b = 0; b < len; ++b) {
+        const u8 c = buf[q];
+        data[dst + b] = c;
+        q += c == (u8)quote ? 2 : 1;
+      }
+    }
+    u64 big = qh_ballot(!pairs && len > 64);
+    while (big) {
+      const int l = __builtin_ctzll(big);
+      big &= big - 1;
+      const u64 s2 = qh_readlane64(src, l);
+      const u32 d2 = qh_readlane32(dst, l), n2 = qh_readlane32(len, l);
+      for (u32 b = lane; b < n2; b += 64) data[d2 + b] = buf[s2 + b];
+    }
+    big = qh_ballot(pairs && wide);
+    while (big) {
+      const int l = __builtin_ctzll(big);
+      big &= big - 1;
+      const u64 s2 = qh_readlane64(src, l);
+      const u32 d2 = qh_readlane32(dst, l), n2 = qh_readlane32(len, l);
+      u64 emitted = 0;
+      u32 carry = 0;
+      for (u64 raw = 0; emitted < n2; raw += 64) {   // (every step emits at least 32 bytes)
+        const u8 c = buf[s2 + raw + lane];
+        const u64 quotes = qh_ballot(c == (u8)quote);
+        const bool drop = qh_csv_undouble_drops(quotes, carry, lane);
+        const u64 dropped = qh_ballot(drop);
+        const u64 o = qh_csv_undouble_out(emitted, dropped, lane);
+        if (!drop && o < n2) data[d2 + o] = c;
+        emitted += (u64)__builtin_popcountll(~dropped);
+        carry = qh_csv_undouble_carry(quotes, carry);
+      }
+    }
+  }
+}
+
 // ---------------------------------------------------------------- launchers
 void launch_csv_scan(const uint8_t* buf, uint64_t d0, uint64_t n, int quote, uint32_t* counts, uint64_t* err, uint64_t* total, hipStream_t s) {
   const uint64_t nchunks = (n + kCsvChunk - 1) / kCsvChunk;
@@ -234,14 +308,30 @@ void launch_csv_decode(const uint8_t* buf, uint64_t n, const uint64_t* starts, u
   if (!nrec) return;
   CsvColsArg a;
   memcpy(&a, &cols, sizeof a);
-  hipLaunchKernelGGL(k_csv_decode, dim3((unsigned)((nrec + QH_BLOCK - 1) / QH_BLOCK)), dim3(QH_BLOCK), 0, s, (const u8*)buf, (u64)n, (const u64*)starts, (u64)nrec,
+  hipLaunchKernelGGL(k_csv_decode<1>, dim3((unsigned)((nrec + QH_BLOCK - 1) / QH_BLOCK)), dim3(QH_BLOCK), 0, s, (const u8*)buf, (u64)n, (const u64*)starts, (u64)nrec,
                      a, ncols, nfields, (u32)delim, (u64*)err, (u64*)null_counts, (u64*)utf8_bytes);
+}
+void launch_csv_decode_q(const uint8_t* buf, uint64_t n, const uint64_t* starts, uint64_t nrec, const CsvCols& cols, int ncols, uint32_t nfields, int delim,
+                         int quote, uint64_t* err, uint64_t* null_counts, uint64_t* utf8_bytes, hipStream_t s) {
+  if (!nrec) return;
+  CsvColsArg a;
+  memcpy(&a, &cols, sizeof a);
+  const u32 dq = (u32)delim | ((u32)(quote + 1) << 8);
+  hipLaunchKernelGGL(k_csv_decode<2>, dim3((unsigned)((nrec + QH_BLOCK - 1) / QH_BLOCK)), dim3(QH_BLOCK), 0, s, (const u8*)buf, (u64)n, (const u64*)starts, (u64)nrec,
+                     a, ncols, nfields, dq, (u64*)err, (u64*)null_counts, (u64*)utf8_bytes);
 }
 void launch_csv_copy_utf8(const uint8_t* buf, const uint64_t* strpos, const uint32_t* offsets, uint64_t nrows, uint8_t* data, hipStream_t s) {
   if (!nrows) return;
   uint64_t g = ((nrows + 63) / 64 * 64 + QH_BLOCK - 1) / QH_BLOCK;
   if (g > 8192) g = 8192;
   hipLaunchKernelGGL(k_csv_copy_utf8, dim3((unsigned)g), dim3(QH_BLOCK), 0, s, (const u8*)buf, (const u64*)strpos, (const u32*)offsets, (u64)nrows, (u8*)data);
+}
+void launch_csv_copy_utf8_q(const uint8_t* buf, const uint64_t* strpos, const uint32_t* offsets, uint64_t nrows, uint8_t* data, int quote, hipStream_t s) {
+  if (!nrows) return;
+  uint64_t g = ((nrows + 63) / 64 * 64 + QH_BLOCK - 1) / QH_BLOCK;
+  if (g > 8192) g = 8192;
+  hipLaunchKernelGGL(k_csv_copy_utf8_q, dim3((unsigned)g), dim3(QH_BLOCK), 0, s, (const u8*)buf, (const u64*)strpos, (const u32*)offsets, (u64)nrows, (u8*)data,
+                     (u32)quote);
 }
 
 }  // namespace qhip

@@ -119,7 +119,9 @@ def read_csv(path: str, options: Optional[CsvReadOptions] = None, schema: Option
 
     device=True (None: the environment's QHIP_CSV_DEVICE, default 0): the file's text is decoded on the device
     (qhip_table_from_csv) and the result's `decoded_on_device` is True; a file outside the device's strict
-    grammar falls back silently to the host parse below, which also produces every error message."""
+    grammar falls back silently to the host parse below, which also produces every error message. What that grammar holds is
+    the context's level (`Context.set_csv_grammar` / QHIP_CSV_GRAMMAR): 1, the default, plain fields only; 2 also quoted fields,
+    Boolean and Timestamp columns — with `schema=None` the types Arrow infers pass through as they are."""
     import os
     o = options or CsvReadOptions()
     if device is None:

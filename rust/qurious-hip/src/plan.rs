@@ -74,6 +74,9 @@ impl HipContext {
         // Join keys of any width too, as HashJoinExec hashes and compares them (hash_join.rs:191-215): both sides are encoded
         // to shared key codes first instead of keeping the single-threaded CPU join
         unsafe { qhip_ctx_set_wide_join_keys(raw, 1) };
+        // CSV text decoded on the device as ordinary writers produce it: quoted fields, and the Boolean and Timestamp columns
+        // that arrow-rs' schema inference yields (datasource/file/csv.rs:56)
+        unsafe { qhip_ctx_set_csv_grammar(raw, 2) };
         Ok(Arc::new(Self { raw, lock: Mutex::new(()), tables: Mutex::new(HashMap::new()) }))
     }
     pub fn raw(&self) -> *mut qhip_ctx {

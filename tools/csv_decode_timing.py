@@ -12,7 +12,11 @@ calls after --warmup calls, each ending in a device synchronise:
 
 (a) .. (c) alternate in one process, --repeat times.
 
-    python tools/csv_decode_timing.py [--gb 1.0] [--runs 10] [--warmup 2] [--repeat 2] [--threads 16]
+--quoted: the same table written with Arrow's default quoting (every string value in quotes) plus a comment column l_comment
+whose values hold commas and, in a few percent of the rows, a doubled quote; the context decodes at grammar level 2
+(qhip_ctx_set_csv_grammar), without which such a file takes the host path.
+
+    python tools/csv_decode_timing.py [--gb 1.0] [--runs 10] [--warmup 2] [--repeat 2] [--threads 16] [--quoted]
 """
 import argparse
 import ctypes as C
@@ -26,6 +30,7 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
+import numpy as np  # noqa: E402
 import pyarrow as pa  # noqa: E402
 import pyarrow.csv as pacsv  # noqa: E402
 
@@ -36,13 +41,31 @@ from qurious_amd._ffi import DeviceTable  # noqa: E402
 PASSES = ["upload", "k_csv_scan", "record starts", "k_csv_decode", "Utf8 offsets + k_csv_copy_utf8"]
 
 
-def write_file(path, target_bytes):
+COMMENT_WORDS = ["carefully", "final deposits", "blithely ironic", "requests, packages", "slyly even", "accounts sleep, furiously", "pending", "quickly"]
+
+
+def comment_column(first_row, n):
+    """TPC-H-like comments of 16 to 80 bytes out of a pool of 4096: every one holds a comma, one in 32 (3 %) a word in quotes"""
+    pool = []
+    for k in range(4096):
+        first = COMMENT_WORDS[k % 8]
+        if k % 32 == 5:
+            first = '"' + first + '"'
+        pool.append(first + ", " + COMMENT_WORDS[(k // 8) % 8] + (" " + COMMENT_WORDS[(k // 64) % 8] if k % 3 else ""))
+    idx = (np.arange(first_row, first_row + n, dtype=np.int64) * 2654435761 >> 7) % len(pool)
+    return pa.array(pool, pa.string()).take(pa.array(idx))
+
+
+def write_file(path, target_bytes, quoted=False):
     """lineitem rows until the file has about target_bytes; returns the row count"""
     step, rows = 1 << 20, 0
     with open(path, "wb") as f:
         while f.tell() < target_bytes:
-            batch = synth.lineitem_batch(rows, step)
-            pacsv.write_csv(pa.Table.from_batches([batch]), f, write_options=pacsv.WriteOptions(include_header=rows == 0, quoting_style="none"))
+            tbl = pa.Table.from_batches([synth.lineitem_batch(rows, step)])
+            if quoted:
+                tbl = tbl.append_column("l_comment", comment_column(rows, step))
+            opts = pacsv.WriteOptions(include_header=rows == 0) if quoted else pacsv.WriteOptions(include_header=rows == 0, quoting_style="none")
+            pacsv.write_csv(tbl, f, write_options=opts)
             rows += step
     return rows
 
@@ -65,17 +88,22 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--repeat", type=int, default=2)
     ap.add_argument("--threads", type=int, default=16)
+    ap.add_argument("--quoted", action="store_true", help="Arrow's default quoting and a comment column with commas and doubled quotes; grammar level 2")
     args = ap.parse_args()
     pa.set_cpu_count(args.threads)
     ctx = q.get_context()
     schema = pa.schema([pa.field(f.name, f.type) for f in synth.LINEITEM_SCHEMA])
+    if args.quoted:
+        schema = schema.append(pa.field("l_comment", pa.string()))
+        ctx.set_csv_grammar(2)
     hip = C.CDLL(None)   # (libqhip.so is loaded globally and brings the HIP runtime with it)
     hip.hipMalloc.argtypes, hip.hipMemcpy.argtypes, hip.hipFree.argtypes = [C.POINTER(C.c_void_p), C.c_size_t], [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int], [C.c_void_p]
     with tempfile.TemporaryDirectory() as d:
         path = os.path.join(d, "lineitem.csv")
-        rows = write_file(path, int(args.gb * 1e9))
+        rows = write_file(path, int(args.gb * 1e9), args.quoted)
         nbytes = os.path.getsize(path)
-        print(f"device {ctx.device_name()}; {path}: {nbytes} bytes, {rows} rows, {nbytes / rows:.1f} bytes per record; median (min) of {args.runs} calls "
+        kind = ", default quoting, grammar 2" if args.quoted else ""
+        print(f"device {ctx.device_name()}; {path}: {nbytes} bytes, {rows} rows, {nbytes / rows:.1f} bytes per record{kind}; median (min) of {args.runs} calls "
               f"after {args.warmup} warm-up calls; host parse with {args.threads} threads", flush=True)
 
         def host_path():
