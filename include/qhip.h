@@ -324,6 +324,33 @@ int qhip_ctx_csv_pass_ms(const qhip_ctx* ctx, double* out, int32_t n_out);
  * Boolean / Timestamp columns, decoded by kernels of their own — level 1 launches what it always launched. The environment's
  * QHIP_CSV_GRAMMAR (1 / 2) is read when the context is created. */
 int qhip_ctx_set_csv_grammar(qhip_ctx* ctx, int32_t level);
+/* Decode a Parquet file ON THE DEVICE into a table (csrc/parquet.cpp; replaces datasource/file/parquet.rs + the
+ * upload). bytes: the whole file in host memory (a read-only mapping will do), read only during the call. schema: a struct
+ * ArrowSchema with the Arrow type of EVERY field of the file, in file order (what Arrow's own reader reports for it). columns /
+ * n_columns: the fields to decode, in output order (NULL / 0 = all); an unprojected column's bytes are not uploaded and nothing of
+ * it is looked at beyond the footer. batch_rows: a batch boundary every batch_rows rows of the table (<= 0: one batch), as the
+ * host path cuts the combined table.
+ * The call is eager and exact or not at all: QHIP_OK with a table whose columns are what qhip_table_from_arrow would hold after
+ * Arrow C++ read the same bytes, or QHIP_UNSUPPORTED with nothing created — the message names the reason and, where it applies,
+ * the row group, column and page — and the caller takes the host path.
+ * Format level 1 is decoded: PAR1 at both ends, a flat schema of optional / required leaves, UNCOMPRESSED projected chunks stored
+ * in this file, per chunk at most one PLAIN dictionary page followed by data pages V1 whose num_values add up to the row group's
+ * rows, RLE definition levels, values PLAIN or RLE_DICTIONARY / PLAIN_DICTIONARY at index widths 0..32 (both within one chunk),
+ * at least one row. Type pairs: INT32 -> Int32, Date32, Int8/Int16/UInt8/UInt16/UInt32, Decimal128(p <= 9); INT64 -> Int64, UInt64,
+ * Timestamp(ms | us | ns) without a zone, Decimal128(p <= 18); FLOAT -> Float32; DOUBLE -> Float64; BOOLEAN -> Boolean; BYTE_ARRAY
+ * with the STRING annotation -> Utf8 (the bytes as they are); FIXED_LEN_BYTE_ARRAY(1..16) DECIMAL -> Decimal128.
+ * Needs the host: a compressed projected chunk (pyarrow's DEFAULT is Snappy: write with compression="NONE"), data pages V2, index
+ * pages, an encrypted footer, a group / list / map field anywhere in the schema, a chunk with file_path, any other encoding
+ * (DELTA_*, BYTE_STREAM_SPLIT, RLE values), BIT_PACKED levels, every other type pair (a zoned Timestamp, Date64, Time, Float16,
+ * Decimal256, INT96, LargeUtf8, Binary, dictionary-typed fields), a stored value outside an Int8/Int16/UInt8/UInt16 column's
+ * range, a Utf8 column over 2^31 - 1 bytes, more than 64 projected columns, 0 rows, 2^32 - 1 rows or more, and every offset,
+ * length, count or index that points outside the file, its chunk, its page or its dictionary ("corrupt"): no host or device
+ * code reads outside the file's bytes because of what the file says. */
+int qhip_table_from_parquet(qhip_ctx* ctx, const struct ArrowSchema* schema, const void* bytes, int64_t n_bytes,
+                            const int32_t* columns, int32_t n_columns, int64_t batch_rows, qhip_table** out);
+/* Device time (ms) of the last qhip_table_from_parquet's five passes — upload, levels, string walk, values, Utf8 — when the
+ * context's timing is on (qhip_ctx_set_timing); zeros otherwise. n_out must be 5. */
+int qhip_ctx_parquet_pass_ms(const qhip_ctx* ctx, double* out, int32_t n_out);
 /* Download batch `batch_index` as a struct ArrowArray (+ schema if out_schema != NULL).
  * Buffers are library-owned host memory freed by the release callbacks.
  * batch_index == -1: every row of the table as ONE array — a caller facing thousands of small batches (the reference's

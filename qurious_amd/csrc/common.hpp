@@ -283,6 +283,8 @@ struct Ctx {
   float wide_join_stage_ms = 0;
   // device time of the last qhip_table_from_csv's passes (csv.cpp; timing on): upload, scan, record starts, decode, Utf8
   float csv_pass_ms[5] = {0, 0, 0, 0, 0};
+  // ... and of the last qhip_table_from_parquet's (parquet.cpp): upload, levels, string walk, values, Utf8
+  float parquet_pass_ms[5] = {0, 0, 0, 0, 0};
   // the device CSV decoder's grammar level (csv.cpp): 1 = plain fields only, 2 = + canonical quoted fields, Boolean, Timestamp;
   // QHIP_CSV_GRAMMAR at context creation, qhip_ctx_set_csv_grammar later
   int csv_grammar = 1;

@@ -1,0 +1,262 @@
+// qhip_parquet.inc — per-run and per-value code of the device Parquet decoder (parquet.cpp qhip_table_from_parquet,
+// kernels_parquet.hip; DESIGN §3.9): the needs-host reasons, the page and column descriptors both sides share, the run headers
+// of the RLE / bit-packed hybrid, bit extraction, the validity word a level run contributes, the physical value readers
+// (little-endian INT32 / INT64, big-endian FIXED_LEN_BYTE_ARRAY decimals) and the checks of a BYTE_ARRAY length chain.
+//
+// One text for two compilers: included by kernels_parquet.hip for hipcc and, as plain host C++, by parquet.cpp and
+// tests/cpp/parquet_tests.cpp, so the functions the kernels call are the functions the CPU tests check under the sanitizers.
+// Self-contained: builtin integer types only, no #include. Every count, length and index in a page is untrusted: each function
+// says which bytes it reads and the caller has checked them against the page before (no load assumes more than 1-byte alignment).
+#ifndef QHIP_PARQUET_INC
+#define QHIP_PARQUET_INC
+#if defined(__HIP__) || defined(__HIPCC_RTC__)
+#define QH_PQ_HD __host__ __device__
+#else
+#define QH_PQ_HD
+#endif
+
+typedef unsigned char pq_u8;
+typedef unsigned int pq_u32;
+typedef unsigned long long pq_u64;
+typedef long long pq_i64;
+
+#define QH_PQ_MAX_COLS 64
+
+// ---- why a file needs the host path (the smallest page << 8 | reason wins on the device, as for CSV)
+#define QH_PQ_OK 0
+#define QH_PQ_R_MAGIC 1            // no PAR1 at both ends, or too short for a footer
+#define QH_PQ_R_ENCRYPTED 2        // PARE: an encrypted footer
+#define QH_PQ_R_CORRUPT 3          // an offset, length or count that points outside the file, its chunk or its page
+#define QH_PQ_R_NESTED 4           // a group, list or map field somewhere in the schema
+#define QH_PQ_R_SCHEMA 5           // the file's fields are not the passed schema's
+#define QH_PQ_R_TYPE 6             // a (physical type, annotation, Arrow type) triple outside the coverage list
+#define QH_PQ_R_CODEC 7            // a projected chunk is compressed
+#define QH_PQ_R_FILE_PATH 8        // a projected chunk lives in another file
+#define QH_PQ_R_PAGE_V2 9
+#define QH_PQ_R_INDEX_PAGE 10
+#define QH_PQ_R_PAGE_ORDER 11      // a second dictionary page, one behind a data page, an unknown page type
+#define QH_PQ_R_ENCODING 12        // a value encoding other than PLAIN / PLAIN_DICTIONARY / RLE_DICTIONARY
+#define QH_PQ_R_LEVEL_ENCODING 13  // BIT_PACKED definition levels
+#define QH_PQ_R_REPEATED 14        // a repeated field: repetition level above 0
+#define QH_PQ_R_NO_ROWS 15
+#define QH_PQ_R_TOO_MANY_COLUMNS 16
+#define QH_PQ_R_TOO_MANY_ROWS 17
+#define QH_PQ_R_NUM_VALUES 18      // a chunk's data pages do not add up to the row group's rows
+#define QH_PQ_R_LEVELS_LENGTH 19   // the levels' length prefix points past the page
+#define QH_PQ_R_RUN 20             // a run header or a run's bytes past the end of its stream, or a run of no values
+#define QH_PQ_R_RUN_COUNT 21       // a level run that counts past num_values
+#define QH_PQ_R_LEVEL_VALUE 22     // a definition level above 1
+#define QH_PQ_R_BIT_WIDTH 23       // dictionary indices wider than 32 bits
+#define QH_PQ_R_VALUES_SHORT 24    // the values region holds fewer values than the page has non-NULL rows
+#define QH_PQ_R_DICT_INDEX 25      // a dictionary index >= the dictionary's entry count
+#define QH_PQ_R_BYTE_ARRAY 26      // a BYTE_ARRAY length that points past its page
+#define QH_PQ_R_RANGE 27           // a stored INT32 outside an Int8 / Int16 / UInt8 / UInt16 column's range
+#define QH_PQ_R_UTF8_LONG 28       // a Utf8 column of more than 2^31 - 1 bytes
+#define QH_PQ_R_COUNT 29
+
+QH_PQ_HD inline const char* qh_pq_reason_text(unsigned r) {
+  switch (r) {
+    case QH_PQ_R_MAGIC: return "no PAR1 magic at both ends";
+    case QH_PQ_R_ENCRYPTED: return "an encrypted footer";
+    case QH_PQ_R_CORRUPT: return "corrupt: an offset, length or count points outside the file, its chunk or its page";
+    case QH_PQ_R_NESTED: return "a group, list or map field in the schema";
+    case QH_PQ_R_SCHEMA: return "the file's fields differ from the schema's";
+    case QH_PQ_R_TYPE: return "a column type that is not decoded on the device";
+    case QH_PQ_R_CODEC: return "a compressed column chunk";
+    case QH_PQ_R_FILE_PATH: return "a column chunk stored in another file";
+    case QH_PQ_R_PAGE_V2: return "a data page V2";
+    case QH_PQ_R_INDEX_PAGE: return "an index page";
+    case QH_PQ_R_PAGE_ORDER: return "a dictionary page that is not the chunk's first page, or an unknown page type";
+    case QH_PQ_R_ENCODING: return "a value encoding other than PLAIN and RLE_DICTIONARY";
+    case QH_PQ_R_LEVEL_ENCODING: return "BIT_PACKED definition levels";
+    case QH_PQ_R_REPEATED: return "a repeated field";
+    case QH_PQ_R_NO_ROWS: return "a file of 0 rows";
+    case QH_PQ_R_TOO_MANY_COLUMNS: return "more than 64 projected columns";
+    case QH_PQ_R_TOO_MANY_ROWS: return "2^32 - 1 rows or more";
+    case QH_PQ_R_NUM_VALUES: return "corrupt: the data pages' num_values do not add up to the row group's rows";
+    case QH_PQ_R_LEVELS_LENGTH: return "corrupt: the levels' length points past the page";
+    case QH_PQ_R_RUN: return "corrupt: a run past the end of its stream";
+    case QH_PQ_R_RUN_COUNT: return "corrupt: a level run counts past num_values";
+    case QH_PQ_R_LEVEL_VALUE: return "a definition level above 1";
+    case QH_PQ_R_BIT_WIDTH: return "corrupt: a dictionary index width above 32 bits";
+    case QH_PQ_R_VALUES_SHORT: return "corrupt: fewer values than non-NULL rows in the page";
+    case QH_PQ_R_DICT_INDEX: return "corrupt: a dictionary index past the dictionary's entries";
+    case QH_PQ_R_BYTE_ARRAY: return "corrupt: a BYTE_ARRAY length points past its page";
+    case QH_PQ_R_RANGE: return "a stored value outside the column's integer range";
+    case QH_PQ_R_UTF8_LONG: return "a Utf8 column larger than 2 GiB";
+    default: return "outside the device's Parquet coverage";
+  }
+}
+
+// ---- descriptors (host: parquet.cpp fills them; device: the kernels read them from device memory)
+#define QH_PQ_ENC_PLAIN 0u
+#define QH_PQ_ENC_DICT 1u       // RLE_DICTIONARY / PLAIN_DICTIONARY indices over the chunk's dictionary page
+#define QH_PQ_ENC_DICTPAGE 2u   // the dictionary page itself: only the string walk looks at it (Utf8)
+
+// physical layout of a stored value
+#define QH_PQ_P_BOOL 0u
+#define QH_PQ_P_32 1u           // 4 bytes little-endian (INT32 sign-extended, FLOAT as its bits)
+#define QH_PQ_P_64 2u           // 8 bytes little-endian
+#define QH_PQ_P_FLBA 3u         // `flba` bytes big-endian two's complement (decimals)
+#define QH_PQ_P_BYTES 4u        // BYTE_ARRAY: 4-byte length, then the bytes
+
+// one page of a projected chunk, in file order within its chunk. Positions are byte offsets into the uploaded buffer.
+typedef struct qh_pq_page {
+  pq_u64 pos;         // the page's payload (behind its header)
+  pq_u64 first_row;   // data page: its first row in the output column
+  pq_u64 dict_pos;    // data page: the chunk's dictionary page payload; dictionary page: unused
+  pq_u64 ent;         // Utf8: where this page's (length, position) entries begin in the column's entry array
+  pq_u32 size;        // payload bytes
+  pq_u32 num_values;  // data page: rows; dictionary page: entries
+  pq_u32 col;         // index into the column descriptors
+  pq_u32 enc;         // QH_PQ_ENC_*
+  pq_u32 dict_size;   // data page: the dictionary payload's bytes
+  pq_u32 dict_n;      // ... and its entry count (fixed widths: dict_n * width <= dict_size was checked on the host)
+} qh_pq_page;
+
+typedef struct qh_pq_ent { pq_u64 pos; pq_u32 len; pq_u32 pad; } qh_pq_ent;   // one BYTE_ARRAY value: its bytes in the buffer
+
+typedef struct qh_pq_col {
+  void* values;       // width-byte values | u32 lengths (Utf8, scanned into offsets afterwards) | Boolean bits (zeroed)
+  pq_u64* valid;      // validity words, zeroed; NULL for a required column
+  pq_u64* strpos;     // Utf8: where row k's bytes lie in the buffer
+  qh_pq_ent* ent;     // Utf8: entries of the PLAIN data pages (at first_row) and of the dictionaries (behind the rows)
+  pq_u32 phys;        // QH_PQ_P_*
+  pq_u32 flba;        // FIXED_LEN_BYTE_ARRAY length 1..16
+  pq_u32 width;       // bytes of an output value: 1, 2, 4, 8, 16 (0: Boolean, Utf8)
+  pq_u32 narrow;      // 0: none; 1: signed, 2: unsigned range check of an INT32 stored for a 1- / 2-byte column
+} qh_pq_col;
+
+// what the level pass leaves for the value passes, per page
+typedef struct qh_pq_state { pq_u32 nonnull; pq_u32 values_off; } qh_pq_state;
+
+// ---- little-endian reads at any alignment
+QH_PQ_HD inline pq_u32 qh_pq_le32(const pq_u8* p) { return (pq_u32)p[0] | ((pq_u32)p[1] << 8) | ((pq_u32)p[2] << 16) | ((pq_u32)p[3] << 24); }
+QH_PQ_HD inline pq_u64 qh_pq_le64(const pq_u8* p) { return (pq_u64)qh_pq_le32(p) | ((pq_u64)qh_pq_le32(p + 4) << 32); }
+
+// ULEB128 of a u32 at s[pos ..), nothing read at or behind s[len]. Returns the bytes consumed, 0 when it does not end in time.
+QH_PQ_HD inline int qh_pq_varint(const pq_u8* s, pq_u64 len, pq_u64 pos, pq_u32* out) {
+  pq_u32 v = 0;
+  for (int i = 0; i < 5; ++i) {
+    if (pos + (pq_u64)i >= len) return 0;
+    const pq_u32 b = s[pos + (pq_u64)i];
+    if (i == 4 && b > 0x0Fu) return 0;
+    v |= (b & 0x7Fu) << (7 * i);
+    if (!(b & 0x80u)) { *out = v; return i + 1; }
+  }
+  return 0;
+}
+
+// ---- the RLE / bit-packed hybrid. A run covers the value indices [start, start + count) of its stream.
+typedef struct qh_pq_run {
+  pq_u64 start, count;
+  pq_u64 data;      // bit-packed: where its bytes begin in the stream (count / 8 * width of them, all inside the stream)
+  pq_u32 value;     // RLE: the repeated value
+  pq_u32 packed;
+} qh_pq_run;
+
+QH_PQ_HD inline void qh_pq_run_init(qh_pq_run* r) { r->start = 0; r->count = 0; r->data = 0; r->value = 0; r->packed = 0; }
+
+// The run behind `r` in the stream s[0 .. len) of bit width w (0..32): parses the header at *cpos, checks that the run's bytes
+// lie inside the stream, moves *cpos behind them. QH_PQ_OK or QH_PQ_R_RUN; a run of no values is refused (no progress).
+QH_PQ_HD inline int qh_pq_next_run(const pq_u8* s, pq_u64 len, pq_u64* cpos, pq_u32 w, qh_pq_run* r) {
+  pq_u32 h = 0;
+  const int used = qh_pq_varint(s, len, *cpos, &h);
+  if (!used) return QH_PQ_R_RUN;
+  const pq_u64 pos = *cpos + (pq_u64)used;
+  r->start += r->count;
+  if (h & 1u) {
+    const pq_u64 groups = h >> 1;
+    const pq_u64 bytes = groups * w;
+    if (!groups || bytes > len - pos) return QH_PQ_R_RUN;
+    r->packed = 1; r->count = groups * 8; r->data = pos; r->value = 0;
+    *cpos = pos + bytes;
+  } else {
+    const pq_u64 vb = (w + 7u) >> 3;
+    if (!(h >> 1) || vb > len - pos) return QH_PQ_R_RUN;
+    pq_u32 v = 0;
+    for (pq_u64 i = 0; i < vb; ++i) v |= (pq_u32)s[pos + i] << (8 * i);
+    r->packed = 0; r->count = h >> 1; r->data = pos; r->value = v;
+    *cpos = pos + vb;
+  }
+  return QH_PQ_OK;
+}
+
+// value k (k < count) of a bit-packed run whose bytes begin at d: w bits at bit k * w. Reads only bytes of the run.
+QH_PQ_HD inline pq_u32 qh_pq_extract(const pq_u8* d, pq_u64 k, pq_u32 w) {
+  if (!w) return 0;
+  const pq_u64 bit = k * w, b = bit >> 3;
+  const pq_u32 sh = (pq_u32)(bit & 7u), nb = (sh + w + 7u) >> 3;   // at most 5 bytes
+  pq_u64 v = 0;
+  for (pq_u32 i = 0; i < nb; ++i) v |= (pq_u64)d[b + i] << (8 * i);
+  return (pq_u32)((v >> sh) & (w == 32 ? 0xFFFFFFFFull : ((1ull << w) - 1ull)));
+}
+
+QH_PQ_HD inline pq_u32 qh_pq_run_value(const pq_u8* s, const qh_pq_run* r, pq_u64 idx, pq_u32 w) {
+  return r->packed ? qh_pq_extract(s + r->data, idx - r->start, w) : r->value;
+}
+
+// The bits a level run (width 1) sets in validity word `word` of the column: the run's first `take` values stand for the rows
+// [g0, g0 + take). 0 where the run does not touch the word. A bit-packed run reads at most 9 of its own bytes.
+QH_PQ_HD inline pq_u64 qh_pq_level_word(const pq_u8* s, const qh_pq_run* r, pq_u64 g0, pq_u64 take, pq_u64 word) {
+  const pq_u64 w0 = word * 64;
+  const pq_u64 lo = w0 > g0 ? w0 : g0, hi = w0 + 64 < g0 + take ? w0 + 64 : g0 + take;
+  if (lo >= hi) return 0;
+  const pq_u32 n = (pq_u32)(hi - lo);
+  pq_u64 bits;
+  if (!r->packed) {
+    bits = r->value ? ~0ull : 0ull;
+  } else {
+    const pq_u64 k = lo - g0, b = k >> 3;
+    const pq_u32 sh = (pq_u32)(k & 7u), nb = (sh + n + 7u) >> 3;   // at most 9 bytes, all below count / 8
+    const pq_u8* d = s + r->data + b;
+    bits = 0;
+    for (pq_u32 i = 0; i < nb && i < 8; ++i) bits |= (pq_u64)d[i] << (8 * i);
+    bits >>= sh;
+    if (nb == 9) bits |= (pq_u64)d[8] << (64 - sh);   // (nb == 9 only with sh > 0)
+  }
+  if (n < 64) bits &= (1ull << n) - 1ull;
+  return bits << (lo & 63u);
+}
+
+// ---- stored values. A value is read as a sign-extended 128-bit integer (lo, hi) and its low `width` bytes are stored.
+QH_PQ_HD inline void qh_pq_read_value(const pq_u8* src, pq_u32 phys, pq_u32 flba, pq_u64* lo, pq_u64* hi) {
+  if (phys == QH_PQ_P_32) {
+    const pq_i64 v = (pq_i64)(int)qh_pq_le32(src);
+    *lo = (pq_u64)v; *hi = v < 0 ? ~0ull : 0ull;
+  } else if (phys == QH_PQ_P_64) {
+    *lo = qh_pq_le64(src); *hi = (*lo >> 63) ? ~0ull : 0ull;
+  } else {
+    // FIXED_LEN_BYTE_ARRAY decimal: flba (1..16) bytes, big-endian two's complement
+    pq_u64 l = (src[0] & 0x80u) ? ~0ull : 0ull, h = l;
+    for (pq_u32 i = 0; i < flba; ++i) { h = (h << 8) | (l >> 56); l = (l << 8) | src[i]; }
+    *lo = l; *hi = h;
+  }
+}
+
+// an INT32 stored for an Int8 / Int16 / UInt8 / UInt16 column must lie in the column's range
+QH_PQ_HD inline bool qh_pq_in_range(pq_u64 lo, pq_u32 width, pq_u32 narrow) {
+  const pq_i64 v = (pq_i64)lo;
+  if (narrow == 1) return width == 1 ? (v >= -128 && v <= 127) : (v >= -32768 && v <= 32767);
+  if (narrow == 2) return width == 1 ? (v >= 0 && v <= 255) : (v >= 0 && v <= 65535);
+  return true;
+}
+
+QH_PQ_HD inline void qh_pq_store(void* values, pq_u64 row, pq_u32 width, pq_u64 lo, pq_u64 hi) {
+  switch (width) {
+    case 1: ((pq_u8*)values)[row] = (pq_u8)lo; break;
+    case 2: ((unsigned short*)values)[row] = (unsigned short)lo; break;
+    case 4: ((pq_u32*)values)[row] = (pq_u32)lo; break;
+    case 8: ((pq_u64*)values)[row] = lo; break;
+    default: ((pq_u64*)values)[2 * row] = lo; ((pq_u64*)values)[2 * row + 1] = hi; break;
+  }
+}
+
+QH_PQ_HD inline pq_u32 qh_pq_phys_bytes(pq_u32 phys, pq_u32 flba) { return phys == QH_PQ_P_32 ? 4u : phys == QH_PQ_P_64 ? 8u : phys == QH_PQ_P_FLBA ? flba : 0u; }
+
+// ---- a BYTE_ARRAY length chain in a region of `size` bytes. Before the 4 length bytes at q are read: has_prefix. Before the
+// length is followed (q becomes q + 4 + len): fits.
+QH_PQ_HD inline bool qh_pq_chain_has_prefix(pq_u64 q, pq_u64 size) { return size >= 4 && q <= size - 4; }
+QH_PQ_HD inline bool qh_pq_chain_fits(pq_u64 q, pq_u64 size, pq_u32 len) { return (pq_u64)len <= size - (q + 4); }
+
+#endif  // QHIP_PARQUET_INC

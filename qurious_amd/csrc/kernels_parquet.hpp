@@ -1,0 +1,22 @@
+// kernels_parquet.hpp — launchers of kernels_parquet.hip (the device Parquet decoder, parquet.cpp). The page, column
+// and state descriptors are the ones of device/qhip_parquet.inc; every pointer is device memory, `buf` the uploaded chunks.
+#pragma once
+#include <hip/hip_runtime_api.h>
+#include <cstdint>
+
+#include "device/qhip_parquet.inc"
+
+namespace qhip {
+
+// definition levels -> validity words (zeroed before), per page its non-NULL count and where its values begin, per column its
+// NULL count. err: the smallest (page << 8 | reason), ~0 when none.
+void launch_pq_levels(const uint8_t* buf, const qh_pq_page* pages, uint32_t npages, const qh_pq_col* cols, qh_pq_state* state, uint64_t* err, uint64_t* null_counts,
+                      hipStream_t s);
+// the BYTE_ARRAY length chains of the Utf8 columns' dictionary pages and PLAIN data pages -> (length, position) entries
+void launch_pq_strings(const uint8_t* buf, uint64_t buf_bytes, const qh_pq_page* pages, uint32_t npages, const qh_pq_col* cols, const qh_pq_state* state, uint64_t* err,
+                       hipStream_t s);
+// values: bit-unpack, dictionary gather, scatter over NULLs; Utf8 rows get (length, position) and the column its byte total
+void launch_pq_values(const uint8_t* buf, const qh_pq_page* pages, uint32_t npages, const qh_pq_col* cols, const qh_pq_state* state, uint64_t* err, uint64_t* utf8_bytes,
+                      hipStream_t s);
+
+}  // namespace qhip

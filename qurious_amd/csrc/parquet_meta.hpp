@@ -1,0 +1,452 @@
+// parquet_meta.hpp — the host half of the device Parquet decoder that needs no device (parquet.cpp includes it; so does
+// tests/cpp/parquet_tests.cpp, which runs it under the sanitizers): a bounds-checked Thrift compact-protocol reader, the footer
+// (FileMetaData) and page headers decoded as far as they are used, the match of a column's physical type and annotation against
+// its Arrow type, and the page walk that turns the projected chunks into a page table. Plain C++, no Arrow, no HIP.
+// Every offset, length and count comes from the file and is checked before it is followed: a violation throws PqNeedsHost.
+#pragma once
+#include <cstdint>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "qhip.h"
+#include "device/qhip_parquet.inc"
+
+namespace qhip_pq {
+
+struct PqNeedsHost {
+  int reason;
+  int64_t row_group, column, page;   // -1: does not apply
+};
+[[noreturn]] inline void needs_host(int reason, int64_t rg = -1, int64_t col = -1, int64_t page = -1) { throw PqNeedsHost{reason, rg, col, page}; }
+
+inline std::string needs_host_text(const PqNeedsHost& e) {
+  std::string s = std::string("Parquet needs the host path: ") + qh_pq_reason_text((unsigned)e.reason);
+  if (e.row_group >= 0) s += ", row group " + std::to_string(e.row_group);
+  if (e.column >= 0) s += ", column " + std::to_string(e.column);
+  if (e.page >= 0) s += ", page " + std::to_string(e.page);
+  return s;
+}
+
+// ---------------------------------------------------------------- Thrift compact protocol
+enum { T_STOP = 0, T_TRUE = 1, T_FALSE = 2, T_BYTE = 3, T_I16 = 4, T_I32 = 5, T_I64 = 6, T_DOUBLE = 7, T_BINARY = 8, T_LIST = 9, T_SET = 10, T_MAP = 11, T_STRUCT = 12 };
+
+struct Thrift {
+  const uint8_t* p;
+  uint64_t n, pos = 0;
+  Thrift(const uint8_t* bytes, uint64_t len) : p(bytes), n(len) {}
+  [[noreturn]] static void bad() { needs_host(QH_PQ_R_CORRUPT); }
+  uint8_t byte() { if (pos >= n) bad(); return p[pos++]; }
+  uint64_t varint() {
+    uint64_t v = 0;
+    for (int shift = 0; shift < 70; shift += 7) {
+      const uint8_t b = byte();
+      v |= (uint64_t)(b & 0x7F) << (shift < 64 ? shift : 63);
+      if (!(b & 0x80)) return v;
+    }
+    bad();
+  }
+  int64_t zigzag() { const uint64_t v = varint(); return (int64_t)(v >> 1) ^ -(int64_t)(v & 1); }
+  // the next field of a struct: false at the stop byte. `last` carries the previous field id (deltas).
+  bool field(int& last, int& id, int& type) {
+    const uint8_t b = byte();
+    if (b == 0) return false;
+    type = b & 0x0F;
+    const int delta = b >> 4;
+    id = delta ? last + delta : (int)zigzag();
+    last = id;
+    return true;
+  }
+  void binary(const uint8_t*& s, uint64_t& len) {
+    len = varint();
+    if (len > n - pos) bad();
+    s = p + pos;
+    pos += len;
+  }
+  std::string string() { const uint8_t* s; uint64_t len; binary(s, len); return std::string((const char*)s, (size_t)len); }
+  // a list's element type and size; every element takes at least one byte, so a size beyond the rest of the bytes is refused
+  // before anything is reserved for it
+  void list(int& elem, uint64_t& size) {
+    const uint8_t b = byte();
+    elem = b & 0x0F;
+    size = b >> 4;
+    if (size == 15) size = varint();
+    if (size > n - pos) bad();
+  }
+  void skip(int type, int depth, bool in_container = false) {
+    if (depth > 24) bad();
+    switch (type) {
+      case T_TRUE: case T_FALSE: if (in_container) (void)byte(); break;   // (a struct field carries its Boolean in the type)
+      case T_BYTE: (void)byte(); break;
+      case T_I16: case T_I32: case T_I64: (void)varint(); break;
+      case T_DOUBLE: if (n - pos < 8) bad(); pos += 8; break;
+      case T_BINARY: { const uint8_t* s; uint64_t len; binary(s, len); break; }
+      case T_LIST: case T_SET: {
+        int elem; uint64_t size;
+        list(elem, size);
+        for (uint64_t i = 0; i < size; ++i) skip(elem, depth + 1, true);
+        break;
+      }
+      case T_MAP: {
+        const uint64_t size = varint();
+        if (size > n - pos) bad();
+        if (size) {
+          const uint8_t kv = byte();
+          for (uint64_t i = 0; i < size; ++i) { skip(kv >> 4, depth + 1, true); skip(kv & 0x0F, depth + 1, true); }
+        }
+        break;
+      }
+      case T_STRUCT: {
+        int last = 0, id, t;
+        while (field(last, id, t)) skip(t, depth + 1);
+        break;
+      }
+      default: bad();
+    }
+  }
+  int64_t integer(int type) { if (type != T_I16 && type != T_I32 && type != T_I64 && type != T_BYTE) bad(); return type == T_BYTE ? (int64_t)(int8_t)byte() : zigzag(); }
+  bool boolean(int type) { if (type != T_TRUE && type != T_FALSE) bad(); return type == T_TRUE; }
+};
+
+// ---------------------------------------------------------------- the parts of the metadata that are used
+enum { PT_BOOLEAN = 0, PT_INT32 = 1, PT_INT64 = 2, PT_INT96 = 3, PT_FLOAT = 4, PT_DOUBLE = 5, PT_BYTE_ARRAY = 6, PT_FLBA = 7 };
+enum { ENC_PLAIN = 0, ENC_PLAIN_DICTIONARY = 2, ENC_RLE = 3, ENC_BIT_PACKED = 4, ENC_RLE_DICTIONARY = 8 };
+enum { PAGE_DATA = 0, PAGE_INDEX = 1, PAGE_DICTIONARY = 2, PAGE_DATA_V2 = 3 };
+enum { L_NONE = 0, L_STRING, L_DECIMAL, L_DATE, L_TIMESTAMP, L_INT, L_OTHER };
+
+struct SchemaElem {
+  int type = -1, type_length = 0, repetition = -1, num_children = 0, converted = -1, scale = 0, precision = 0;
+  std::string name;
+  int logical = L_NONE;             // the annotation, from logicalType where present, else from converted_type
+  int bits = 0, is_signed = 0;      // L_INT
+  int unit = 0, utc = 0;            // L_TIMESTAMP: 1 ms, 2 us, 3 ns
+};
+struct Chunk {
+  bool has_file_path = false, has_meta = false;
+  int type = -1, codec = -1;
+  int64_t num_values = -1, total_compressed = -1, data_off = -1, dict_off = -1;
+};
+struct RowGroup { std::vector<Chunk> cols; int64_t num_rows = -1; };
+struct Footer { std::vector<SchemaElem> schema; int64_t num_rows = -1; std::vector<RowGroup> groups; };
+struct PageHeader {
+  int type = -1;
+  int64_t uncompressed = -1, compressed = -1;
+  bool has_data = false, has_dict = false;
+  int64_t num_values = -1, encoding = -1, def_encoding = -1;   // of the data or dictionary page header
+  uint64_t header_bytes = 0;
+};
+
+inline void read_logical_type(Thrift& t, SchemaElem& e) {
+  int last = 0, id, ty;
+  while (t.field(last, id, ty)) {
+    if (ty != T_STRUCT) { t.skip(ty, 1); continue; }
+    int l2 = 0, id2, ty2;
+    switch (id) {
+      case 1: e.logical = L_STRING; break;
+      case 5: e.logical = L_DECIMAL; break;
+      case 6: e.logical = L_DATE; break;
+      case 8: e.logical = L_TIMESTAMP; e.utc = 1; e.unit = 0; break;
+      case 10: e.logical = L_INT; break;
+      default: e.logical = L_OTHER; break;
+    }
+    while (t.field(l2, id2, ty2)) {
+      if (id == 5 && id2 == 1) e.scale = (int)t.integer(ty2);
+      else if (id == 5 && id2 == 2) e.precision = (int)t.integer(ty2);
+      else if (id == 8 && id2 == 1) e.utc = t.boolean(ty2) ? 1 : 0;
+      else if (id == 8 && id2 == 2 && ty2 == T_STRUCT) {
+        int l3 = 0, id3, ty3;
+        while (t.field(l3, id3, ty3)) { e.unit = id3; t.skip(ty3, 3); }
+      } else if (id == 10 && id2 == 1) e.bits = (int)t.integer(ty2);
+      else if (id == 10 && id2 == 2) e.is_signed = t.boolean(ty2) ? 1 : 0;
+      else t.skip(ty2, 2);
+    }
+  }
+}
+
+inline SchemaElem read_schema_elem(Thrift& t) {
+  SchemaElem e;
+  bool has_logical = false;
+  int last = 0, id, ty;
+  while (t.field(last, id, ty)) {
+    switch (id) {
+      case 1: e.type = (int)t.integer(ty); break;
+      case 2: e.type_length = (int)t.integer(ty); break;
+      case 3: e.repetition = (int)t.integer(ty); break;
+      case 4: if (ty != T_BINARY) Thrift::bad(); e.name = t.string(); break;
+      case 5: e.num_children = (int)t.integer(ty); break;
+      case 6: e.converted = (int)t.integer(ty); break;
+      case 7: if (!has_logical) e.scale = (int)t.integer(ty); else (void)t.integer(ty); break;
+      case 8: if (!has_logical) e.precision = (int)t.integer(ty); else (void)t.integer(ty); break;
+      case 10: if (ty != T_STRUCT) Thrift::bad(); read_logical_type(t, e); has_logical = true; break;
+      default: t.skip(ty, 1); break;
+    }
+  }
+  if (!has_logical && e.converted >= 0) {
+    const int c = e.converted;
+    if (c == 0) e.logical = L_STRING;
+    else if (c == 5) e.logical = L_DECIMAL;
+    else if (c == 6) e.logical = L_DATE;
+    else if (c == 9 || c == 10) { e.logical = L_TIMESTAMP; e.utc = 1; e.unit = c - 8; }   // (legacy annotation: Arrow reads these as UTC)
+    else if (c >= 11 && c <= 14) { e.logical = L_INT; e.is_signed = 0; e.bits = 8 << (c - 11); }
+    else if (c >= 15 && c <= 18) { e.logical = L_INT; e.is_signed = 1; e.bits = 8 << (c - 15); }
+    else e.logical = L_OTHER;
+  }
+  return e;
+}
+
+inline Chunk read_chunk(Thrift& t) {
+  Chunk c;
+  int last = 0, id, ty;
+  while (t.field(last, id, ty)) {
+    if (id == 1 && ty == T_BINARY) { (void)t.string(); c.has_file_path = true; }
+    else if (id == 3 && ty == T_STRUCT) {
+      c.has_meta = true;
+      int l2 = 0, id2, ty2;
+      while (t.field(l2, id2, ty2)) {
+        switch (id2) {
+          case 1: c.type = (int)t.integer(ty2); break;
+          case 4: c.codec = (int)t.integer(ty2); break;
+          case 5: c.num_values = t.integer(ty2); break;
+          case 7: c.total_compressed = t.integer(ty2); break;
+          case 9: c.data_off = t.integer(ty2); break;
+          case 11: c.dict_off = t.integer(ty2); break;
+          default: t.skip(ty2, 2); break;   // (encodings, path_in_schema, key_value_metadata, Statistics, ...)
+        }
+      }
+    } else t.skip(ty, 1);
+  }
+  return c;
+}
+
+inline Footer read_footer(const uint8_t* bytes, uint64_t len) {
+  Thrift t(bytes, len);
+  Footer f;
+  int last = 0, id, ty;
+  while (t.field(last, id, ty)) {
+    if (id == 2 && ty == T_LIST) {
+      int elem; uint64_t size;
+      t.list(elem, size);
+      if (elem != T_STRUCT) Thrift::bad();
+      for (uint64_t i = 0; i < size; ++i) f.schema.push_back(read_schema_elem(t));
+    } else if (id == 3) f.num_rows = t.integer(ty);
+    else if (id == 4 && ty == T_LIST) {
+      int elem; uint64_t size;
+      t.list(elem, size);
+      if (elem != T_STRUCT) Thrift::bad();
+      for (uint64_t i = 0; i < size; ++i) {
+        RowGroup g;
+        int l2 = 0, id2, ty2;
+        while (t.field(l2, id2, ty2)) {
+          if (id2 == 1 && ty2 == T_LIST) {
+            int e2; uint64_t s2;
+            t.list(e2, s2);
+            if (e2 != T_STRUCT) Thrift::bad();
+            for (uint64_t k = 0; k < s2; ++k) g.cols.push_back(read_chunk(t));
+          } else if (id2 == 3) g.num_rows = t.integer(ty2);
+          else t.skip(ty2, 2);
+        }
+        f.groups.push_back(std::move(g));
+      }
+    } else t.skip(ty, 1);
+  }
+  return f;
+}
+
+// one page header in bytes[0 .. len): nothing behind len is read
+inline PageHeader read_page_header(const uint8_t* bytes, uint64_t len) {
+  Thrift t(bytes, len);
+  PageHeader h;
+  int last = 0, id, ty;
+  while (t.field(last, id, ty)) {
+    if (id == 1) h.type = (int)t.integer(ty);
+    else if (id == 2) h.uncompressed = t.integer(ty);
+    else if (id == 3) h.compressed = t.integer(ty);
+    else if ((id == 5 || id == 7) && ty == T_STRUCT) {
+      (id == 5 ? h.has_data : h.has_dict) = true;
+      int l2 = 0, id2, ty2;
+      while (t.field(l2, id2, ty2)) {
+        if (id2 == 1) h.num_values = t.integer(ty2);
+        else if (id2 == 2) h.encoding = t.integer(ty2);
+        else if (id2 == 3 && id == 5) h.def_encoding = t.integer(ty2);
+        else t.skip(ty2, 2);   // (Statistics, is_sorted, the repetition level encoding: a flat column has none)
+      }
+    } else t.skip(ty, 1);
+  }
+  h.header_bytes = t.pos;
+  return h;
+}
+
+// ---------------------------------------------------------------- types
+struct ArrowType { int id = -1; int precision = 0, scale = 0; };   // id: a QHIP_* dtype id; -1: a type the C ABI does not carry
+
+struct ColPlan {
+  uint32_t phys = 0, flba = 0, width = 0, narrow = 0;
+  bool optional = true, utf8 = false, boolean = false;
+  uint64_t dict_entries = 0;   // Utf8: entries of all its dictionary pages
+};
+
+// does the file store Arrow type `a` in this leaf the way the device decodes? Fills the column's physical description.
+inline bool match_type(const SchemaElem& e, const ArrowType& a, ColPlan& c) {
+  const int L = e.logical;
+  auto is_int = [&](int bits, int sg) { return L == L_INT && e.bits == bits && e.is_signed == sg; };
+  switch (a.id) {
+    case QHIP_BOOL: c.phys = QH_PQ_P_BOOL; c.boolean = true; return e.type == PT_BOOLEAN && L == L_NONE;
+    case QHIP_INT8: c.phys = QH_PQ_P_32; c.width = 1; c.narrow = 1; return e.type == PT_INT32 && is_int(8, 1);
+    case QHIP_INT16: c.phys = QH_PQ_P_32; c.width = 2; c.narrow = 1; return e.type == PT_INT32 && is_int(16, 1);
+    case QHIP_UINT8: c.phys = QH_PQ_P_32; c.width = 1; c.narrow = 2; return e.type == PT_INT32 && is_int(8, 0);
+    case QHIP_UINT16: c.phys = QH_PQ_P_32; c.width = 2; c.narrow = 2; return e.type == PT_INT32 && is_int(16, 0);
+    case QHIP_INT32: c.phys = QH_PQ_P_32; c.width = 4; return e.type == PT_INT32 && (L == L_NONE || is_int(32, 1));
+    case QHIP_UINT32: c.phys = QH_PQ_P_32; c.width = 4; return e.type == PT_INT32 && is_int(32, 0);
+    case QHIP_DATE32: c.phys = QH_PQ_P_32; c.width = 4; return e.type == PT_INT32 && L == L_DATE;
+    case QHIP_FLOAT32: c.phys = QH_PQ_P_32; c.width = 4; return e.type == PT_FLOAT && L == L_NONE;
+    case QHIP_INT64: c.phys = QH_PQ_P_64; c.width = 8; return e.type == PT_INT64 && (L == L_NONE || is_int(64, 1));
+    case QHIP_UINT64: c.phys = QH_PQ_P_64; c.width = 8; return e.type == PT_INT64 && is_int(64, 0);
+    case QHIP_FLOAT64: c.phys = QH_PQ_P_64; c.width = 8; return e.type == PT_DOUBLE && L == L_NONE;
+    case QHIP_TIMESTAMP_MS: case QHIP_TIMESTAMP_US: case QHIP_TIMESTAMP_NS:
+      c.phys = QH_PQ_P_64; c.width = 8;
+      return e.type == PT_INT64 && L == L_TIMESTAMP && !e.utc && e.unit == a.id - QHIP_TIMESTAMP_MS + 1;
+    case QHIP_UTF8: c.phys = QH_PQ_P_BYTES; c.utf8 = true; return e.type == PT_BYTE_ARRAY && L == L_STRING;
+    case QHIP_DECIMAL128:
+      c.width = 16;
+      if (L != L_DECIMAL || e.precision != a.precision || e.scale != a.scale || a.precision < 1 || a.precision > 38) return false;
+      if (e.type == PT_INT32) { c.phys = QH_PQ_P_32; return a.precision <= 9; }
+      if (e.type == PT_INT64) { c.phys = QH_PQ_P_64; return a.precision <= 18; }
+      c.phys = QH_PQ_P_FLBA; c.flba = (uint32_t)e.type_length;
+      return e.type == PT_FLBA && e.type_length >= 1 && e.type_length <= 16;
+    default: return false;
+  }
+}
+
+// ---------------------------------------------------------------- the plan: which bytes to upload, which pages they hold
+struct Range { uint64_t file_off, bytes, buf_off; };
+struct PageWhere { int64_t row_group, column, page; };
+
+struct Plan {
+  uint64_t num_rows = 0;
+  uint64_t upload_bytes = 0;
+  std::vector<ColPlan> cols;          // in output order
+  std::vector<Range> ranges;          // the projected chunks, one behind the other in the upload buffer
+  std::vector<qh_pq_page> pages;      // (`col`: index into cols; positions in the upload buffer)
+  std::vector<PageWhere> where;       // for the message: what pages[k] is in the file
+};
+
+// names: the schema's field names (checked against the file's when given). types: the Arrow type of EVERY field. proj: the
+// fields to decode, in output order.
+inline Plan plan_file(const uint8_t* file, uint64_t n, const std::vector<std::string>* names, const std::vector<ArrowType>& types, const std::vector<int32_t>& proj) {
+  if (n >= 4 && memcmp(file, "PARE", 4) == 0) needs_host(QH_PQ_R_ENCRYPTED);
+  if (n >= 4 && memcmp(file + n - 4, "PARE", 4) == 0) needs_host(QH_PQ_R_ENCRYPTED);
+  if (n < 12 || memcmp(file, "PAR1", 4) != 0 || memcmp(file + n - 4, "PAR1", 4) != 0) needs_host(QH_PQ_R_MAGIC);
+  const uint64_t flen = qh_pq_le32(file + n - 8);
+  if (flen > n - 12) needs_host(QH_PQ_R_CORRUPT);
+  const uint64_t fstart = n - 8 - flen;   // data lies in [4, fstart)
+  const Footer f = read_footer(file + fstart, flen);
+
+  // ---- the schema: a root and leaves, nothing else
+  if (f.schema.empty()) needs_host(QH_PQ_R_CORRUPT);
+  for (size_t k = 1; k < f.schema.size(); ++k) {
+    const SchemaElem& e = f.schema[k];
+    if (e.num_children > 0 || e.type < 0) needs_host(QH_PQ_R_NESTED);
+    if (e.repetition == 2) needs_host(QH_PQ_R_REPEATED);
+    if (e.repetition != 0 && e.repetition != 1) needs_host(QH_PQ_R_CORRUPT);
+  }
+  const size_t nfields = f.schema.size() - 1;
+  if ((size_t)f.schema[0].num_children != nfields) needs_host(QH_PQ_R_NESTED);
+  if (nfields != types.size()) needs_host(QH_PQ_R_SCHEMA);
+  if (names) for (size_t k = 0; k < nfields; ++k) if (f.schema[k + 1].name != (*names)[k]) needs_host(QH_PQ_R_SCHEMA);
+  if (proj.size() > QH_PQ_MAX_COLS) needs_host(QH_PQ_R_TOO_MANY_COLUMNS);
+
+  Plan plan;
+  for (size_t k = 0; k < proj.size(); ++k) {
+    ColPlan c;
+    const SchemaElem& e = f.schema[(size_t)proj[k] + 1];
+    if (e.type == PT_INT96 || !match_type(e, types[(size_t)proj[k]], c)) needs_host(QH_PQ_R_TYPE, -1, proj[k]);
+    c.optional = e.repetition == 1;
+    plan.cols.push_back(c);
+  }
+
+  // ---- rows
+  uint64_t rows = 0;
+  for (const RowGroup& g : f.groups) {
+    if (g.num_rows < 0 || (uint64_t)g.num_rows > 0xFFFFFFFFull) needs_host(g.num_rows < 0 ? QH_PQ_R_CORRUPT : QH_PQ_R_TOO_MANY_ROWS);
+    rows += (uint64_t)g.num_rows;
+    if (rows >= 0xFFFFFFFFull) needs_host(QH_PQ_R_TOO_MANY_ROWS);
+  }
+  if (f.num_rows < 0 || (uint64_t)f.num_rows != rows) needs_host(QH_PQ_R_CORRUPT);
+  if (rows == 0) needs_host(QH_PQ_R_NO_ROWS);
+  plan.num_rows = rows;
+
+  // ---- the page walk: one header per page of every projected chunk
+  uint64_t first_row = 0;
+  for (size_t gi = 0; gi < f.groups.size(); ++gi) {
+    const RowGroup& g = f.groups[gi];
+    if (g.num_rows == 0) continue;
+    if (g.cols.size() != nfields) needs_host(QH_PQ_R_CORRUPT, (int64_t)gi);
+    for (size_t k = 0; k < proj.size(); ++k) {
+      const Chunk& ch = g.cols[(size_t)proj[k]];
+      ColPlan& cp = plan.cols[k];
+      const int64_t G = (int64_t)gi, C = proj[k];
+      if (ch.has_file_path) needs_host(QH_PQ_R_FILE_PATH, G, C);
+      if (!ch.has_meta || ch.type != f.schema[(size_t)proj[k] + 1].type) needs_host(QH_PQ_R_CORRUPT, G, C);
+      if (ch.codec != 0) needs_host(QH_PQ_R_CODEC, G, C);
+      const int64_t start = ch.dict_off > 0 ? ch.dict_off : ch.data_off;
+      if (start < 4 || ch.total_compressed < 0 || (uint64_t)start > fstart || (uint64_t)ch.total_compressed > fstart - (uint64_t)start) needs_host(QH_PQ_R_CORRUPT, G, C);
+      const uint64_t cbytes = (uint64_t)ch.total_compressed, cbuf = plan.upload_bytes;
+      plan.ranges.push_back(Range{(uint64_t)start, cbytes, cbuf});
+      plan.upload_bytes += cbytes;
+      const uint8_t* chunk = file + start;
+      const uint32_t pw = qh_pq_phys_bytes(cp.phys, cp.flba);
+      uint64_t pos = 0, got = 0, dict_pos = 0, dict_ent = 0;
+      uint32_t dict_size = 0, dict_n = 0;
+      bool have_dict = false, seen_data = false;
+      for (int64_t pageno = 0; got < (uint64_t)g.num_rows; ++pageno) {
+        if (pos >= cbytes) needs_host(QH_PQ_R_NUM_VALUES, G, C, pageno);
+        PageHeader h;
+        try { h = read_page_header(chunk + pos, cbytes - pos); } catch (const PqNeedsHost& e) { needs_host(e.reason, G, C, pageno); }
+        const uint64_t payload = pos + h.header_bytes;
+        if (h.compressed < 0 || h.compressed != h.uncompressed || (uint64_t)h.compressed > cbytes - payload || h.compressed > 0x7FFFFFFF)
+          needs_host(QH_PQ_R_CORRUPT, G, C, pageno);
+        const uint32_t size = (uint32_t)h.compressed;
+        qh_pq_page pg;
+        memset(&pg, 0, sizeof pg);
+        pg.pos = cbuf + payload; pg.size = size; pg.col = (uint32_t)k;
+        if (h.type == PAGE_DICTIONARY) {
+          if (have_dict || seen_data) needs_host(QH_PQ_R_PAGE_ORDER, G, C, pageno);
+          if (!h.has_dict || h.num_values < 0 || h.num_values > 0x7FFFFFFF) needs_host(QH_PQ_R_CORRUPT, G, C, pageno);
+          if ((h.encoding != ENC_PLAIN && h.encoding != ENC_PLAIN_DICTIONARY) || cp.boolean) needs_host(QH_PQ_R_ENCODING, G, C, pageno);
+          // (fixed widths: every entry lies inside the page; BYTE_ARRAY: every entry has at least its 4 length bytes, which
+          // bounds the entry array, and the string walk checks each length)
+          if ((uint64_t)h.num_values * (cp.utf8 ? 4u : pw) > size) needs_host(QH_PQ_R_CORRUPT, G, C, pageno);
+          have_dict = true;
+          dict_pos = pg.pos; dict_size = size; dict_n = (uint32_t)h.num_values;
+          dict_ent = plan.num_rows + cp.dict_entries;
+          cp.dict_entries += dict_n;
+          pg.enc = QH_PQ_ENC_DICTPAGE; pg.num_values = dict_n; pg.ent = dict_ent;
+        } else if (h.type == PAGE_DATA) {
+          if (!h.has_data || h.num_values < 0) needs_host(QH_PQ_R_CORRUPT, G, C, pageno);
+          if ((uint64_t)h.num_values > (uint64_t)g.num_rows - got) needs_host(QH_PQ_R_NUM_VALUES, G, C, pageno);
+          if (h.encoding == ENC_PLAIN) pg.enc = QH_PQ_ENC_PLAIN;
+          else if ((h.encoding == ENC_RLE_DICTIONARY || h.encoding == ENC_PLAIN_DICTIONARY) && !cp.boolean) {
+            if (!have_dict) needs_host(QH_PQ_R_CORRUPT, G, C, pageno);
+            pg.enc = QH_PQ_ENC_DICT;
+          } else needs_host(QH_PQ_R_ENCODING, G, C, pageno);
+          if (cp.optional && h.def_encoding != ENC_RLE) needs_host(h.def_encoding == ENC_BIT_PACKED ? QH_PQ_R_LEVEL_ENCODING : QH_PQ_R_CORRUPT, G, C, pageno);
+          seen_data = true;
+          pg.num_values = (uint32_t)h.num_values; pg.first_row = first_row + got;
+          pg.dict_pos = dict_pos; pg.dict_size = dict_size; pg.dict_n = dict_n;
+          pg.ent = pg.enc == QH_PQ_ENC_DICT ? dict_ent : pg.first_row;
+          got += (uint64_t)h.num_values;
+        } else if (h.type == PAGE_DATA_V2) needs_host(QH_PQ_R_PAGE_V2, G, C, pageno);
+        else if (h.type == PAGE_INDEX) needs_host(QH_PQ_R_INDEX_PAGE, G, C, pageno);
+        else needs_host(QH_PQ_R_PAGE_ORDER, G, C, pageno);
+        plan.pages.push_back(pg);
+        plan.where.push_back(PageWhere{G, C, pageno});
+        if (plan.pages.size() >= (1u << 24)) needs_host(QH_PQ_R_CORRUPT, G, C, pageno);   // (the device's error word keeps 8 bits for the reason)
+        pos = payload + size;
+      }
+    }
+    first_row += (uint64_t)g.num_rows;
+  }
+  return plan;
+}
+
+}  // namespace qhip_pq

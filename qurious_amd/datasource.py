@@ -9,6 +9,8 @@ for TPC-H Q1 that is 7 of lineitem's 16 columns. Parquet additionally skips the 
 
 CSV files can instead be decoded ON THE DEVICE (`read_csv(device=True)` / QHIP_CSV_DEVICE=1, off by default): the
 text crosses PCIe once and unread columns are never parsed; a file outside the device's strict grammar takes the host path.
+So can Parquet files (`read_parquet(device=True)` / QHIP_PARQUET_DEVICE=1, off by default): only the projected
+column chunks cross PCIe; format level 1 (uncompressed, data pages V1, flat columns), everything else takes the host path.
 
 Divergence note: with `schema=None` the column types come from Arrow C++'s CSV / JSON type inference, which is close to
 but not the same code as arrow-rs' `Format::infer_schema` (csv.rs:58); pass an explicit schema for exact control."""
@@ -37,9 +39,9 @@ def _table_of(tbl: pa.Table, batch_rows: Optional[int]) -> MemoryTable:
     return MemoryTable(tbl.schema, batches, lazy_upload=True)
 
 
-class DeviceCsvTable(MemoryTable):
-    """A CSV file decoded on the device (qhip_table_from_csv): `device_table()` IS the decoded table, nothing was parsed on
-    the host. `.data` — what the oracle, `insert` and `delete` work on — is downloaded the first time somebody asks for it;
+class DeviceDecodedTable(MemoryTable):
+    """A file decoded on the device (qhip_table_from_csv, qhip_table_from_parquet): `device_table()` IS the decoded table, nothing
+    was parsed on the host. `.data` — what the oracle, `insert` and `delete` work on — is downloaded the first time somebody asks for it;
     from then on MemoryTable's rule holds (the device copy is kept for as long as `data` holds the very batches it stands for)."""
 
     decoded_on_device = True
@@ -66,6 +68,9 @@ class DeviceCsvTable(MemoryTable):
         if self._data is None:
             return self._device
         return super().device_table()
+
+
+DeviceCsvTable = DeviceDecodedTable   # (the name it had when CSV was the only format decoded on the device)
 
 
 def _host_read_csv(path, o, schema, batch_rows, columns) -> MemoryTable:
@@ -135,10 +140,53 @@ def read_csv(path: str, options: Optional[CsvReadOptions] = None, schema: Option
     return t
 
 
-def read_parquet(path: str, columns: Optional[Sequence[str]] = None, batch_rows: Optional[int] = 1 << 20) -> MemoryTable:
-    """read_parquet (datasource/file/parquet.rs): `columns` (optional) is a projection applied while reading the file"""
+def _device_read_parquet(path, columns, batch_rows) -> Optional[MemoryTable]:
+    """the device path, or None when the file needs the host path (QHIP_UNSUPPORTED, or a file Arrow itself cannot open)"""
+    import mmap
+    import os
     import pyarrow.parquet as pq
-    return _table_of(pq.read_table(path, columns=list(columns) if columns else None), batch_rows)
+    from ._ffi import UnsupportedError, get_context
+    try:
+        schema = pq.read_schema(path)
+        if os.path.getsize(path) == 0:
+            return None
+    except (pa.ArrowException, OSError):
+        return None
+    idx = None
+    if columns:
+        idx = [schema.get_field_index(c) for c in columns]
+        if any(k < 0 for k in idx):
+            return None
+    with open(path, "rb") as f, mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ) as m:
+        try:
+            dev = DeviceTable.from_parquet_bytes(get_context(), schema.remove_metadata(), m, columns=idx, batch_rows=batch_rows)
+        except UnsupportedError:
+            return None
+    # the schema as the host read returns it (its metadata included), cut to the projection
+    out_schema = schema if idx is None else pa.schema([schema.field(k) for k in idx], metadata=schema.metadata)
+    return DeviceDecodedTable(out_schema, dev)
+
+
+def read_parquet(path: str, columns: Optional[Sequence[str]] = None, batch_rows: Optional[int] = 1 << 20, device: Optional[bool] = None) -> MemoryTable:
+    """read_parquet (datasource/file/parquet.rs): `columns` (optional) is a projection applied while reading the file.
+
+    device=True (None: the environment's QHIP_PARQUET_DEVICE, default 0): the footer and one header per page are read on the
+    host, the bytes of the projected column chunks alone cross PCIe and the pages are decoded on the device
+    (qhip_table_from_parquet); the result's `decoded_on_device` is True. The device decodes format level 1:
+    UNCOMPRESSED chunks — write with `compression="NONE"`; pyarrow's default, Snappy, takes the host path — data pages V1, PLAIN
+    and dictionary encodings, flat columns. Every other file falls back silently to the host read below, which also produces
+    every error message."""
+    import os
+    import pyarrow.parquet as pq
+    if device is None:
+        device = os.environ.get("QHIP_PARQUET_DEVICE", "0") not in ("", "0")
+    if device:
+        t = _device_read_parquet(path, columns, batch_rows)
+        if t is not None:
+            return t
+    t = _table_of(pq.read_table(path, columns=list(columns) if columns else None), batch_rows)
+    t.decoded_on_device = False
+    return t
 
 
 def read_json(path: str, batch_rows: Optional[int] = 1 << 20) -> MemoryTable:

@@ -1,0 +1,134 @@
+"""What getting a Parquet table onto the device costs: about --gb GB of lineitem-shaped rows (synth.lineitem written
+once with pyarrow.parquet, compression="NONE", row groups of 2^20 rows, into a temporary directory), and per measurement the
+median of --runs calls after --warmup calls, each ending in a device synchronise:
+
+  (a) host path    datasource.read_parquet(device=False) — Arrow C++ read with --threads threads — plus the eager upload of the
+                   decoded columns
+  (b) device path  datasource.read_parquet(device=True) as a whole call: read_schema, mmap, footer and page walk, upload of the
+                   projected chunks, the kernels, the one host wait
+  (c) floor        one plain host-to-device copy of as many bytes as the projected chunks have, out of the same mapping
+                   (hipMemcpy, pageable source)
+  (d) passes       HIP events around the device path's passes (timing on, calls of their own): upload, k_pq_levels, k_pq_strings,
+                   k_pq_values, Utf8 (offset scans + k_csv_copy_utf8), with the GB/s of chunk bytes each pass amounts to
+
+(a) .. (c) alternate in one process, --repeat times. --columns a,b,c reads a projection: the other columns' chunks stay on disk.
+
+    python tools/parquet_decode_timing.py [--gb 1.0] [--runs 10] [--warmup 2] [--repeat 2] [--threads 16] [--columns l_quantity,l_shipdate]
+"""
+import argparse
+import ctypes as C
+import mmap
+import os
+import statistics
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import pyarrow as pa  # noqa: E402
+import pyarrow.parquet as pq  # noqa: E402
+
+import qurious_amd as q  # noqa: E402
+from qurious_amd import datasource, synth  # noqa: E402
+from qurious_amd._ffi import DeviceTable  # noqa: E402
+
+PASSES = ["upload", "k_pq_levels", "k_pq_strings", "k_pq_values", "Utf8 offsets + k_csv_copy_utf8"]
+
+
+def write_file(path, target_bytes):
+    """lineitem rows, one row group per 2^20 of them, until the file has about target_bytes; returns the row count"""
+    step, rows = 1 << 20, 0
+    schema = pa.schema([pa.field(f.name, f.type) for f in synth.LINEITEM_SCHEMA])
+    with pq.ParquetWriter(path, schema, compression="NONE") as w:
+        while True:
+            w.write_table(pa.Table.from_batches([synth.lineitem_batch(rows, step)]).cast(schema), row_group_size=step)
+            rows += step
+            if os.path.getsize(path) >= target_bytes:
+                return rows
+
+
+def median_ms(fn, runs, warmup):
+    for _ in range(warmup):
+        fn()
+    out = []
+    for _ in range(runs):
+        t0 = time.perf_counter()
+        fn()
+        out.append((time.perf_counter() - t0) * 1e3)
+    return statistics.median(out), min(out)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--gb", type=float, default=1.0)
+    ap.add_argument("--runs", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--repeat", type=int, default=2)
+    ap.add_argument("--threads", type=int, default=16)
+    ap.add_argument("--columns", type=str, default="", help="comma-separated projection (default: every column)")
+    args = ap.parse_args()
+    pa.set_cpu_count(args.threads)
+    columns = [c for c in args.columns.split(",") if c] or None
+    ctx = q.get_context()
+    hip = C.CDLL(None)   # (libqhip.so is loaded globally and brings the HIP runtime with it)
+    hip.hipMalloc.argtypes, hip.hipMemcpy.argtypes, hip.hipFree.argtypes = [C.POINTER(C.c_void_p), C.c_size_t], [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int], [C.c_void_p]
+    with tempfile.TemporaryDirectory() as d:
+        path = os.path.join(d, "lineitem.parquet")
+        rows = write_file(path, int(args.gb * 1e9))
+        nbytes = os.path.getsize(path)
+        md = pq.ParquetFile(path).metadata
+        names = md.schema.names
+        want = set(columns) if columns else set(names)
+        chunk_bytes = sum(md.row_group(g).column(c).total_compressed_size for g in range(md.num_row_groups) for c in range(md.num_columns) if names[c] in want)
+        print(f"device {ctx.device_name()}; {path}: {nbytes} bytes, {rows} rows in {md.num_row_groups} row groups, columns {sorted(want)}: {chunk_bytes} bytes of "
+              f"projected chunks; median (min) of {args.runs} calls after {args.warmup} warm-up calls; host read with {args.threads} threads", flush=True)
+
+        def host_path():
+            t = datasource.read_parquet(path, columns, device=False)
+            dev = DeviceTable.from_batches(ctx, t.schema(), t.data, lazy=False)
+            ctx.synchronize()
+            return dev
+
+        def device_path():
+            t = datasource.read_parquet(path, columns, device=True)
+            assert t.decoded_on_device
+            ctx.synchronize()
+            return t.device_table()
+
+        dst = C.c_void_p()
+        assert hip.hipMalloc(C.byref(dst), chunk_bytes + 64) == 0
+        f = open(path, "rb")
+        m = mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ)
+        src = pa.py_buffer(m)
+
+        def floor():
+            assert hip.hipMemcpy(dst, C.c_void_p(src.address), chunk_bytes, 1) == 0   # (hipMemcpyHostToDevice; returns when the copy is done)
+
+        assert host_path().num_rows == device_path().num_rows == rows
+        for rep in range(args.repeat):
+            for name, fn in (("(a) host read + upload", host_path), ("(b) device path, whole call", device_path), ("(c) plain copy of the chunks", floor)):
+                med, low = median_ms(fn, args.runs, args.warmup)
+                print(f"run {rep + 1} {name:30s} {med:9.2f} ms (min {low:9.2f})  {chunk_bytes / med / 1e6:8.2f} GB/s of chunk bytes", flush=True)
+        ctx.set_timing(True)
+        per = []
+        for _ in range(args.warmup + args.runs):
+            device_path()
+            per.append(ctx.parquet_pass_ms())
+        ctx.set_timing(False)
+        per = per[args.warmup:]
+        kernels = 0.0
+        for k, name in enumerate(PASSES):
+            med = statistics.median(p[k] for p in per)
+            kernels += med if k else 0.0
+            print(f"(d) {name:32s} {med:9.3f} ms  {chunk_bytes / max(med, 1e-6) / 1e6:9.1f} GB/s of chunk bytes", flush=True)
+        print(f"(d) kernels together (all but the upload) {kernels:9.3f} ms  {chunk_bytes / max(kernels, 1e-6) / 1e6:9.1f} GB/s of chunk bytes", flush=True)
+        del src
+        m.close()
+        f.close()
+        hip.hipFree(dst)
+
+
+if __name__ == "__main__":
+    main()
