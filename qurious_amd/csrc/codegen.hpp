@@ -3,12 +3,19 @@
 #pragma once
 #include <map>
 #include <memory>
+#include <sstream>
 #include <string>
 #include <vector>
 
+#include "agg_shape.hpp"
 #include "expr.hpp"
 
 namespace qhip {
+
+struct KeyDesc;
+// the integer-valued types (dates and times among them) as far as casts, key words, MIN / MAX images and sort keys go
+bool intlike(const DType& t);
+bool signed_intlike(const DType& t);
 
 // what a generated kernel needs bound at launch: which table column sits in KArgs.c[slot], literal values
 struct KernelBindings {
@@ -42,6 +49,10 @@ class ExprGen {
   void set_streaming_loads(bool on) { nt_ = on; }
   void mark_utf8_key(int node, int words) { utf8_key_words_[node] = words; }
   bool raw_key_prefetched(int node) const { return raw_ && utf8_key_words_.count(node) > 0; }
+  // what the software-pipelined kernels (aggregate, mask, probe, partition) set up: tile-relative addressing (a uniform 64-bit
+  // tile base in SGPRs + a 32-bit lane offset, so a load needs one VALU instruction for its address instead of a 64-bit
+  // multiply-add chain per column), raw mode, and the bytes of plain Utf8 key columns fetched with the row's other loads
+  void use_tile_loads(const std::vector<KeyDesc>& keys);
   std::string raw_fields, load_code;
   static std::string ctype(const DType& t);
   static std::string i128_const(i128 v);
@@ -50,6 +61,23 @@ class ExprGen {
   int col_slot(int table_col);
   int lit_slot(const ENode& n);
   int str_slot(const std::string& bytes);   // a literal slot holding only string bytes (LIKE patterns)
+  // one per node kind (exprgen.cpp): the node's children go to `out` first, its own statements to `o`
+  void emit_column(int k, const ENode& n, std::ostringstream& o);
+  void emit_utf8_column(int k, const ENode& n, const std::string& S, std::ostringstream& ld, std::ostringstream& o);
+  void emit_value_column(int k, const ENode& n, const std::string& S, std::ostringstream& ld, std::ostringstream& o);
+  void emit_literal(int k, const ENode& n, std::ostringstream& o);
+  void emit_binary(int k, const ENode& n, std::string& out, std::ostringstream& o);
+  void emit_compare(int k, const ENode& n, std::ostringstream& o);
+  void emit_kleene(int k, const ENode& n, std::ostringstream& o);
+  void emit_decimal_arith(int k, const ENode& n, std::ostringstream& o);
+  void emit_float_arith(int k, const ENode& n, std::ostringstream& o);
+  void emit_int_arith(int k, const ENode& n, std::ostringstream& o);
+  void emit_cast(int k, const ENode& n, std::string& out, std::ostringstream& o);
+  void emit_if(int k, const ENode& n, std::string& out, std::ostringstream& o);
+  void emit_like(int k, const ENode& n, std::string& out, std::ostringstream& o);
+  void emit_function(int k, const ENode& n, std::string& out, std::ostringstream& o);
+  void emit_negative(int k, const ENode& n, std::string& out, std::ostringstream& o);
+  void raw_field(const std::string& type, const std::string& name) { if (raw_) raw_fields += "    " + type + " " + name + ";\n"; }   // a member of `Raw`
   const ExprSet& es_;
   const std::vector<InputCol>& in_;
   std::vector<bool> done_;
@@ -68,19 +96,10 @@ int packed_key_words(const DType& t, int utf8_max_len);
 bool packed_key_fits(const std::vector<InputCol>& input, const int32_t* cols, int n);   // the plain key columns `cols` of `input` as ONE aggregate key
 void check_key_type(const DType& t);   // the reference's hasher types (utils/array.rs:190-210), its error text otherwise
 
-// ---------------------------------------------------------------- aggregate plan
-enum CellKind { CELL_ROWS = 0, CELL_SUM_I128, CELL_SUM_U64, CELL_SUM_F64, CELL_CNT, CELL_MAXORD64, CELL_MAXORD128 };
-
+// ---------------------------------------------------------------- aggregate plan (CellKind, ArgDesc, CellDesc: agg_shape.hpp)
 struct KeyDesc {
   int root; DType type; bool nullable;
   int word_off;   // first key word (after the optional null-mask word)
-  int words;
-};
-struct ArgDesc { int root; DType type; bool nullable; };
-struct CellDesc {
-  int kind; int arg;   // arg = index into args (-1 for CELL_ROWS)
-  bool is_min;         // MAXORD cells: true stores ~ord(v) so that the running maximum is the minimum
-  int off;             // word offset inside the slot's cell area
   int words;
 };
 struct AggDesc {
