@@ -339,7 +339,11 @@ int qhip_ctx_set_csv_grammar(qhip_ctx* ctx, int32_t level);
  * at least one row. Type pairs: INT32 -> Int32, Date32, Int8/Int16/UInt8/UInt16/UInt32, Decimal128(p <= 9); INT64 -> Int64, UInt64,
  * Timestamp(ms | us | ns) without a zone, Decimal128(p <= 18); FLOAT -> Float32; DOUBLE -> Float64; BOOLEAN -> Boolean; BYTE_ARRAY
  * with the STRING annotation -> Utf8 (the bytes as they are); FIXED_LEN_BYTE_ARRAY(1..16) DECIMAL -> Decimal128.
- * Needs the host: a compressed projected chunk (pyarrow's DEFAULT is Snappy: write with compression="NONE"), data pages V2, index
+ * Format level 2 (qhip_ctx_set_parquet_format below; off by default) adds projected chunks whose codec is SNAPPY, what pyarrow
+ * writes by default: their pages cross PCIe compressed and are unpacked on the device; a page whose stream is damaged, or which
+ * claims more than 64/3 times its compressed size, needs the host ("Snappy").
+ * Needs the host: a compressed projected chunk (level 1: every codec, so write with compression="NONE" or set level 2; level 2:
+ * every codec but SNAPPY — zstd, gzip, lz4, brotli), data pages V2, index
  * pages, an encrypted footer, a group / list / map field anywhere in the schema, a chunk with file_path, any other encoding
  * (DELTA_*, BYTE_STREAM_SPLIT, RLE values), BIT_PACKED levels, every other type pair (a zoned Timestamp, Date64, Time, Float16,
  * Decimal256, INT96, LargeUtf8, Binary, dictionary-typed fields), a stored value outside an Int8/Int16/UInt8/UInt16 column's
@@ -351,6 +355,24 @@ int qhip_table_from_parquet(qhip_ctx* ctx, const struct ArrowSchema* schema, con
 /* Device time (ms) of the last qhip_table_from_parquet's five passes — upload, levels, string walk, values, Utf8 — when the
  * context's timing is on (qhip_ctx_set_timing); zeros otherwise. n_out must be 5. */
 int qhip_ctx_parquet_pass_ms(const qhip_ctx* ctx, double* out, int32_t n_out);
+/* Device time (ms) of the unpack pass (format level 2: Snappy pages -> the unpack area) of the last qhip_table_from_parquet, or of
+ * the last qhip_snappy_decode's kernel, when the context's timing is on; 0 otherwise and for a file without Snappy pages. The
+ * pass runs between "upload" and "levels" and belongs to neither of qhip_ctx_parquet_pass_ms's five values. */
+int qhip_ctx_parquet_unpack_ms(const qhip_ctx* ctx, double* out);
+/* The format qhip_table_from_parquet decodes. level 1 (the default): uncompressed chunks only. level 2: also SNAPPY chunks,
+ * unpacked by a kernel of its own — a file without them launches what level 1 launches. Any other level answers
+ * QHIP_INVALID_ARGUMENT and leaves the level as it was. The environment's QHIP_PARQUET_FORMAT (1 / 2) is read when the context
+ * is created. */
+int qhip_ctx_set_parquet_format(qhip_ctx* ctx, int32_t level);
+/* A testing and measurement aid: the device Snappy decoder of format level 2 over raw Snappy streams (no framing, as a Parquet
+ * page holds them). bytes: the n_streams streams, stream k in bytes[src_offsets[k] .. src_offsets[k + 1]); dst_sizes[k]: the
+ * uncompressed size the caller declares for it (a page header's uncompressed_page_size). The streams are uploaded, unpacked one
+ * wavefront each after the checks the page walk makes (the preamble equals the declared size, which is at most 64/3 times the
+ * compressed size), and downloaded one behind the other into out (out_bytes >= the sum of dst_sizes). status[k]: 0, or the
+ * Parquet needs-host reason (QH_PQ_R_SNAPPY_*, csrc/device/qhip_parquet.inc) for which stream k was refused — a refused stream
+ * is a normal return, its bytes in out are unspecified, and the other streams of the call are decoded all the same. */
+int qhip_snappy_decode(qhip_ctx* ctx, const void* bytes, int64_t n_bytes, const int64_t* src_offsets, const int64_t* dst_sizes,
+                       int64_t n_streams, void* out, int64_t out_bytes, int32_t* status);
 /* Download batch `batch_index` as a struct ArrowArray (+ schema if out_schema != NULL).
  * Buffers are library-owned host memory freed by the release callbacks.
  * batch_index == -1: every row of the table as ONE array — a caller facing thousands of small batches (the reference's

@@ -152,6 +152,9 @@ def load_library() -> C.CDLL:
             "qhip_ctx_csv_pass_ms": (C.c_int, [vp, P(C.c_double), i32]),
             "qhip_table_from_parquet": (C.c_int, [vp, vp, vp, i64, P(i32), i32, i64, P(vp)]),
             "qhip_ctx_parquet_pass_ms": (C.c_int, [vp, P(C.c_double), i32]),
+            "qhip_ctx_parquet_unpack_ms": (C.c_int, [vp, P(C.c_double)]),
+            "qhip_ctx_set_parquet_format": (C.c_int, [vp, i32]),
+            "qhip_snappy_decode": (C.c_int, [vp, vp, i64, P(i64), P(i64), i64, vp, i64, P(i32)]),
             "qhip_table_to_arrow": (C.c_int, [vp, vp, i64, vp, vp]),
             "qhip_table_num_batches": (i64, [vp]),
             "qhip_table_batch_offsets": (C.c_int, [vp, P(i64), i64]),
@@ -282,6 +285,39 @@ class Context:
         out = (C.c_double * 5)()
         self.check(self.lib.qhip_ctx_parquet_pass_ms(self.handle, out, 5))
         return list(out)
+
+    def parquet_unpack_ms(self) -> float:
+        """Device time (ms) of the unpack pass (Snappy pages, format level 2) of the last device Parquet decode, or of the last
+        `snappy_decode`'s kernel (timing on). It lies between "upload" and "levels" and is part of neither."""
+        out = C.c_double(0)
+        self.check(self.lib.qhip_ctx_parquet_unpack_ms(self.handle, C.byref(out)))
+        return float(out.value)
+
+    def set_parquet_format(self, level: int):
+        """The device Parquet decoder's format level: 1 (the default) uncompressed chunks only, a compressed file needs the host;
+        2 also SNAPPY chunks — pyarrow's default — unpacked on the device. QHIP_PARQUET_FORMAT sets it when the context is made."""
+        self.check(self.lib.qhip_ctx_set_parquet_format(self.handle, int(level)))
+
+    def snappy_decode(self, streams: Sequence[bytes], dst_sizes: Sequence[int]):
+        """A testing and measurement aid (qhip_snappy_decode): raw Snappy streams through the device decoder of format level 2,
+        one wavefront each, in one call. `dst_sizes[k]`: the uncompressed size declared for stream k. Returns (outputs, statuses):
+        statuses[k] is 0 or the needs-host reason (QH_PQ_R_SNAPPY_*) for which stream k was refused, outputs[k] its bytes
+        (None when refused)."""
+        n = len(streams)
+        data = b"".join(streams)
+        off = (C.c_int64 * (n + 1))()
+        for k, s in enumerate(streams):
+            off[k + 1] = off[k] + len(s)
+        dst = (C.c_int64 * max(n, 1))(*[int(v) for v in dst_sizes])
+        total = sum(int(v) for v in dst_sizes if 0 <= int(v) <= 0x7FFFFFFF)
+        out = C.create_string_buffer(max(total, 1))
+        status = (C.c_int32 * max(n, 1))()
+        self.check(self.lib.qhip_snappy_decode(self.handle, data, len(data), off, dst, n, out, total, status))
+        outs, at, raw = [], 0, out.raw
+        for k in range(n):
+            outs.append(raw[at:at + int(dst_sizes[k])] if status[k] == 0 else None)
+            at += int(dst_sizes[k])
+        return outs, [int(status[k]) for k in range(n)]
 
     def sync_count(self) -> int:
         """Host waits on the device made through the library so far (the difference around a plan = its round trips)."""

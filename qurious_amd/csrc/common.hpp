@@ -285,6 +285,11 @@ struct Ctx {
   float csv_pass_ms[5] = {0, 0, 0, 0, 0};
   // ... and of the last qhip_table_from_parquet's (parquet.cpp): upload, levels, string walk, values, Utf8
   float parquet_pass_ms[5] = {0, 0, 0, 0, 0};
+  // ... and of its unpack pass (k_pq_unsnap, between "upload" and "levels"): 0 for a file without Snappy pages
+  float parquet_unpack_ms = 0;
+  // the device Parquet decoder's format level (parquet.cpp): 1 = uncompressed chunks only, 2 = + SNAPPY chunks;
+  // QHIP_PARQUET_FORMAT at context creation, qhip_ctx_set_parquet_format later
+  int parquet_format = 1;
   // the device CSV decoder's grammar level (csv.cpp): 1 = plain fields only, 2 = + canonical quoted fields, Boolean, Timestamp;
   // QHIP_CSV_GRAMMAR at context creation, qhip_ctx_set_csv_grammar later
   int csv_grammar = 1;

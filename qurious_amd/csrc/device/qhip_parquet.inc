@@ -52,7 +52,14 @@ typedef long long pq_i64;
 #define QH_PQ_R_BYTE_ARRAY 26      // a BYTE_ARRAY length that points past its page
 #define QH_PQ_R_RANGE 27           // a stored INT32 outside an Int8 / Int16 / UInt8 / UInt16 column's range
 #define QH_PQ_R_UTF8_LONG 28       // a Utf8 column of more than 2^31 - 1 bytes
-#define QH_PQ_R_COUNT 29
+// (format level 2: a Snappy page, device/qhip_snappy.inc. QH_PQ_R_SNAPPY_BASE + QH_SNAP_E_*)
+#define QH_PQ_R_SNAPPY_BASE 28
+#define QH_PQ_R_SNAPPY_PREAMBLE 29 // the stream's preamble does not end, or is not the header's uncompressed_page_size
+#define QH_PQ_R_SNAPPY_SIZE 30     // uncompressed_page_size above 64/3 times the compressed payload
+#define QH_PQ_R_SNAPPY_INPUT 31    // an element past the end of its stream, or stream and page do not end together
+#define QH_PQ_R_SNAPPY_OUTPUT 32   // an element past uncompressed_page_size
+#define QH_PQ_R_SNAPPY_OFFSET 33   // a copy offset of 0 or beyond the bytes produced
+#define QH_PQ_R_COUNT 34
 
 QH_PQ_HD inline const char* qh_pq_reason_text(unsigned r) {
   switch (r) {
@@ -84,6 +91,11 @@ QH_PQ_HD inline const char* qh_pq_reason_text(unsigned r) {
     case QH_PQ_R_BYTE_ARRAY: return "corrupt: a BYTE_ARRAY length points past its page";
     case QH_PQ_R_RANGE: return "a stored value outside the column's integer range";
     case QH_PQ_R_UTF8_LONG: return "a Utf8 column larger than 2 GiB";
+    case QH_PQ_R_SNAPPY_PREAMBLE: return "corrupt: a Snappy page whose preamble does not end or differs from uncompressed_page_size";
+    case QH_PQ_R_SNAPPY_SIZE: return "corrupt: a Snappy page that claims more than 64/3 times its compressed size";
+    case QH_PQ_R_SNAPPY_INPUT: return "corrupt: a Snappy element past the end of its page, or a page whose stream and size do not end together";
+    case QH_PQ_R_SNAPPY_OUTPUT: return "corrupt: a Snappy element past uncompressed_page_size";
+    case QH_PQ_R_SNAPPY_OFFSET: return "corrupt: a Snappy copy offset of 0 or beyond the bytes produced";
     default: return "outside the device's Parquet coverage";
   }
 }
@@ -100,7 +112,8 @@ QH_PQ_HD inline const char* qh_pq_reason_text(unsigned r) {
 #define QH_PQ_P_FLBA 3u         // `flba` bytes big-endian two's complement (decimals)
 #define QH_PQ_P_BYTES 4u        // BYTE_ARRAY: 4-byte length, then the bytes
 
-// one page of a projected chunk, in file order within its chunk. Positions are byte offsets into the uploaded buffer.
+// one page of a projected chunk, in file order within its chunk. Positions are byte offsets into the device buffer: the
+// uploaded chunks and, behind them, the unpack area. A page of a Snappy chunk is described as it lies unpacked in its slot there.
 typedef struct qh_pq_page {
   pq_u64 pos;         // the page's payload (behind its header)
   pq_u64 first_row;   // data page: its first row in the output column
@@ -113,6 +126,16 @@ typedef struct qh_pq_page {
   pq_u32 dict_size;   // data page: the dictionary payload's bytes
   pq_u32 dict_n;      // ... and its entry count (fixed widths: dict_n * width <= dict_size was checked on the host)
 } qh_pq_page;
+
+// one compressed page (format level 2): k_pq_unsnap turns buffer[src .. src + src_size) into buffer[dst .. dst + dst_size)
+typedef struct qh_pq_unpack {
+  pq_u64 src;         // the compressed payload, in the uploaded chunks
+  pq_u64 dst;         // the page's slot in the unpack area, 16-byte aligned
+  pq_u32 src_size;
+  pq_u32 dst_size;    // uncompressed_page_size: what the stream's preamble says (checked on the host)
+  pq_u32 page;        // index into the page table (the offender word)
+  pq_u32 start;       // bytes of the preamble: where the elements begin in the payload
+} qh_pq_unpack;
 
 typedef struct qh_pq_ent { pq_u64 pos; pq_u32 len; pq_u32 pad; } qh_pq_ent;   // one BYTE_ARRAY value: its bytes in the buffer
 

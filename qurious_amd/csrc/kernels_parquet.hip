@@ -4,6 +4,7 @@
 //
 // The unit of parallelism is the page: one wavefront each. Serial work happens per run header and per BYTE_ARRAY length prefix
 // only; the values of a run are spread over the lanes.
+//   k_pq_unsnap   format level 2 only: a Snappy page of the uploaded chunks -> its uncompressed bytes in the unpack area
 //   k_pq_levels   RLE / bit-packed definition levels -> validity words, the page's non-NULL count, the column's NULL count
 //   k_pq_strings  the length chain of a Utf8 dictionary page or PLAIN data page, staged through LDS -> (length, position)
 //   k_pq_values   64 rows per step: rank among the non-NULL rows -> value index -> run cursor -> dictionary gather or PLAIN read
@@ -15,6 +16,7 @@
 #include "device/qhip_status.h"
 #include "device/qhip_device.hpp"
 #include "kernels_parquet.hpp"
+#include "device/qhip_snappy.inc"
 
 namespace qhip {
 
@@ -131,6 +133,77 @@ __global__ __launch_bounds__(64) void k_pq_strings(const u8* __restrict__ buf, u
   if (reason && lane == 0) pq_report(err, page, reason);
 }
 
+// Format level 2: one wavefront (a workgroup of its own) unpacks one Snappy page from the uploaded chunks into its slot of the
+// unpack area, both in `buf`. The walk over the elements is serial and wave-uniform — input position, output position and the
+// element are the same in every lane: the tag and its length or offset bytes are read from a 1 KB tile of the input staged in
+// LDS as k_pq_strings stages its chains, and a literal that lies inside the tile is taken from there. The bytes of an element
+// are spread over the lanes: a literal in strides of 64, four loads in flight per lane; a copy (at most 64 bytes) in one step,
+// lane l taking the byte qh_snap_copy_src names, which earlier elements stored — never this one.
+// Those bytes were stored by other lanes of this wavefront and are read back from global memory. That rests on one rule: a
+// wavefront's vector memory instructions are issued in program order to the one L1 of its CU, write-through, so a load behind a
+// store of the same wavefront returns the stored bytes whichever lane stored them (LLVM's AMDGPU memory model for gfx90a / gfx942:
+// no action is needed for coherence between the lanes of a wavefront). The wavefront-scope fence per element keeps the compiler
+// to the same order and costs no instruction. So `buf` is neither const nor __restrict__ here.
+// Checks come before every access (qh_snap_check); a refused page leaves its slot half written, which the later passes read as
+// they read any page: untrusted, inside the slot. status (the raw-stream entry): 0 or the error per stream, where not null.
+__global__ __launch_bounds__(64) void k_pq_unsnap(u8* buf, u64 buf_bytes, const qh_pq_unpack* __restrict__ tab, u32 n, u64* err, u32* status) {
+  __shared__ __attribute__((aligned(16))) u8 tile[kPqTile];
+  const u32 k = blockIdx.x;
+  if (k >= n) return;
+  const qh_pq_unpack u = tab[k];
+  const u32 lane = (u32)qh_lane();
+  const u8* src = buf + u.src;
+  u8* dst = buf + u.dst;
+  const u64 n_in = u.src_size, n_out = u.dst_size;
+  u64 ip = u.start, op = 0, tbase = ~0ULL;
+  u32 reason = QH_SNAP_OK;
+  while (ip < n_in) {
+    if (op == n_out) { reason = QH_SNAP_E_INPUT; break; }   // (input left behind a full page)
+    const u64 at = u.src + ip;
+    if (tbase == ~0ULL || at < tbase || at + 5 > tbase + kPqTile) {
+      __syncthreads();
+      tbase = at & ~(u64)15;
+      // (a vector that begins inside the buffer may reach 15 bytes past it: the allocation's slack)
+      const u64 o = (u64)lane * 16;
+      if (tbase + o < buf_bytes) *(pq_v4u*)(tile + o) = *(const pq_v4u*)(buf + tbase + o);
+      __syncthreads();
+    }
+    qh_snap_elem e;
+    reason = (u32)qh_snap_element(tile + (at - tbase), n_in - ip, &e);
+    if (reason) break;
+    ip += e.header;
+    reason = (u32)qh_snap_check(&e, n_in - ip, op, n_out);
+    if (reason) break;
+    if (e.kind == QH_SNAP_LITERAL) {
+      const u64 from = u.src + ip;
+      if (from + e.len <= tbase + kPqTile) {
+        for (u64 i = lane; i < e.len; i += 64) dst[op + i] = tile[from - tbase + i];
+      } else {
+        const u8* s = src + ip;
+        u8* d = dst + op;
+        for (u64 i = lane; i < e.len; i += 256) {
+          const bool h1 = i + 64 < e.len, h2 = i + 128 < e.len, h3 = i + 192 < e.len;
+          const u8 b0 = s[i], b1 = h1 ? s[i + 64] : (u8)0, b2 = h2 ? s[i + 128] : (u8)0, b3 = h3 ? s[i + 192] : (u8)0;
+          d[i] = b0;
+          if (h1) d[i + 64] = b1;
+          if (h2) d[i + 128] = b2;
+          if (h3) d[i + 192] = b3;
+        }
+      }
+      ip += e.len;
+    } else if ((u64)lane < e.len) {
+      dst[op + lane] = dst[qh_snap_copy_src(op, e.offset, lane)];
+    }
+    op += e.len;
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  }
+  if (!reason && op != n_out) reason = QH_SNAP_E_INPUT;   // (the input ended with output missing)
+  if (lane == 0) {
+    if (status) status[k] = reason;
+    if (reason && err) pq_report(err, u.page, QH_PQ_R_SNAPPY_BASE + reason);
+  }
+}
+
 // One wavefront per data page, 64 rows per step, the steps aligned to the column's 64-row words: a lane's row is word * 64 +
 // lane, its validity bit is bit `lane` of one word, and a Boolean column's word is one ballot. The lane's value index is the
 // page's running non-NULL count plus its rank in the step. Dictionary pages: a run cursor moves forward under wave-uniform
@@ -229,6 +302,10 @@ void launch_pq_levels(const uint8_t* buf, const qh_pq_page* pages, uint32_t npag
   if (!npages) return;
   const unsigned g = (unsigned)(((uint64_t)npages * 64 + QH_BLOCK - 1) / QH_BLOCK);
   hipLaunchKernelGGL(k_pq_levels, dim3(g), dim3(QH_BLOCK), 0, s, (const u8*)buf, pages, (u32)npages, cols, state, (u64*)err, (u64*)null_counts);
+}
+void launch_pq_unsnap(uint8_t* buf, uint64_t buf_bytes, const qh_pq_unpack* tab, uint32_t n, uint64_t* err, uint32_t* status, hipStream_t s) {
+  if (!n) return;
+  hipLaunchKernelGGL(k_pq_unsnap, dim3(n), dim3(64), 0, s, (u8*)buf, (u64)buf_bytes, tab, (u32)n, (u64*)err, (u32*)status);
 }
 void launch_pq_strings(const uint8_t* buf, uint64_t buf_bytes, const qh_pq_page* pages, uint32_t npages, const qh_pq_col* cols, const qh_pq_state* state, uint64_t* err,
                        hipStream_t s) {

@@ -4,11 +4,14 @@
 // decoded columns). Here the host reads the footer and one header per page of the projected chunks (parquet_meta.hpp: a Thrift
 // compact reader and the page walk, plain C++), uploads the bytes of those chunks alone — an unprojected column never crosses
 // PCIe — and the device turns pages into columns. Format level 1: uncompressed chunks, data pages V1, PLAIN and dictionary
-// encodings, RLE definition levels, flat columns. Whatever lies outside makes the whole call answer QHIP_UNSUPPORTED with nothing
+// encodings, RLE definition levels, flat columns. Format level 2 (qhip_ctx_set_parquet_format) adds SNAPPY chunks: their pages
+// are uploaded compressed and unpacked on the device into an unpack area behind the uploaded chunks in the same buffer, where
+// the passes below read them as they read any page. Whatever lies outside makes the whole call answer QHIP_UNSUPPORTED with nothing
 // created, and the caller takes the host path, which then produces every error message.
 //
 // Passes, all on the context's stream:
 //   1 upload        the projected chunks, one behind the other, into one device buffer; the page table and column descriptors
+//  (k_pq_unsnap    level 2, a file with Snappy pages only: one wavefront per page, into the unpack area)
 //   2 k_pq_levels   definition levels -> validity words, non-NULL count per page, NULL count per column
 //   3 k_pq_strings  Utf8: the length chains of dictionary pages and PLAIN data pages -> (length, position) entries
 //   4 k_pq_values   values: bit-unpack, dictionary gather, scatter over NULLs; Utf8 rows get (length, position)
@@ -25,6 +28,7 @@
 namespace qhip {
 
 static_assert(sizeof(qh_pq_page) == 56 && sizeof(qh_pq_col) == 48 && sizeof(qh_pq_ent) == 16, "the Parquet descriptors have the layout both compilers agree on");
+static_assert(sizeof(qh_pq_unpack) == 32, "the unpack-table entry has the layout both compilers agree on");
 
 qhip_table* table_from_parquet(Ctx* ctx, const ArrowSchema* schema, const uint8_t* bytes, int64_t n_bytes, const int32_t* columns, int32_t n_columns,
                                int64_t batch_rows) {
@@ -59,7 +63,7 @@ qhip_table* table_from_parquet(Ctx* ctx, const ArrowSchema* schema, const uint8_
   // ---- footer and page walk (host, one header per page)
   qhip_pq::Plan plan;
   try {
-    plan = qhip_pq::plan_file(bytes, (uint64_t)n_bytes, &names, types, proj);
+    plan = qhip_pq::plan_file(bytes, (uint64_t)n_bytes, &names, types, proj, ctx->parquet_format);
   } catch (const qhip_pq::PqNeedsHost& e) {
     fail(QHIP_UNSUPPORTED, qhip_pq::needs_host_text(e));
   }
@@ -79,8 +83,9 @@ qhip_table* table_from_parquet(Ctx* ctx, const ArrowSchema* schema, const uint8_
   ctx->stats_timing_pending = 0;
   ctx->wide_join_stage_ms = 0;
   for (float& ms : ctx->parquet_pass_ms) ms = 0;
-  hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int k = 0; k < 6; ++k) if (e[k]) (void)hipEventDestroy(e[k]); } } ev_guard{ev};
+  ctx->parquet_unpack_ms = 0;
+  hipEvent_t ev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // ([6]: behind the unpack pass)
+  struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int k = 0; k < 7; ++k) if (e[k]) (void)hipEventDestroy(e[k]); } } ev_guard{ev};
   auto mark = [&](int k) {
     if (!ctx->timing) return;
     if (!ev[k]) QHIP_HIP_CHECK(hipEventCreate(&ev[k]));
@@ -89,8 +94,11 @@ qhip_table* table_from_parquet(Ctx* ctx, const ArrowSchema* schema, const uint8_
   time_mark(ctx, 0);
   mark(0);
 
-  // ---- 1. upload: the projected chunks only (the buffer keeps the 64 bytes of slack DevBuf::alloc gives)
-  DevBuf file((size_t)plan.upload_bytes);
+  // ---- 1. upload: the projected chunks only (the buffer keeps the 64 bytes of slack DevBuf::alloc gives); behind them the
+  // unpack area of a file with Snappy pages, which nothing uploads
+  const uint64_t buf_bytes = plan.buffer_bytes();
+  const uint32_t nunpack = (uint32_t)plan.unpack.size();
+  DevBuf file((size_t)buf_bytes);
   const size_t kPiece = 64u << 20;
   for (const qhip_pq::Range& r : plan.ranges)
     for (uint64_t o = 0; o < r.bytes; o += kPiece)
@@ -98,9 +106,11 @@ qhip_table* table_from_parquet(Ctx* ctx, const ArrowSchema* schema, const uint8_
                                     ctx->stream));
   DevBuf pages_d((size_t)npages * sizeof(qh_pq_page)), state_d((size_t)npages * sizeof(qh_pq_state)), cols_d(ncols * sizeof(qh_pq_col));
   QHIP_HIP_CHECK(hipMemcpyAsync(pages_d.ptr, plan.pages.data(), (size_t)npages * sizeof(qh_pq_page), hipMemcpyHostToDevice, ctx->stream));
-  // status words: [0] first offender (page << 8 | reason), [1 .. 1 + 64) NULL counts, then Utf8 byte totals
-  std::vector<uint64_t> st_host(1 + 2 * QH_PQ_MAX_COLS, 0);
-  st_host[0] = ~0ULL;
+  // status words: [0] first offender (page << 8 | reason), [1 .. 1 + 64) NULL counts, then Utf8 byte totals, then the unpack
+  // pass's own first offender
+  const size_t kUnpackWord = 1 + 2 * QH_PQ_MAX_COLS;
+  std::vector<uint64_t> st_host(kUnpackWord + 1, 0);
+  st_host[0] = st_host[kUnpackWord] = ~0ULL;
   DevBuf st(st_host.size() * 8);
   QHIP_HIP_CHECK(hipMemcpyAsync(st.ptr, st_host.data(), st.bytes, hipMemcpyHostToDevice, ctx->stream));
   uint64_t* st_dev = st.as<uint64_t>();
@@ -137,22 +147,33 @@ qhip_table* table_from_parquet(Ctx* ctx, const ArrowSchema* schema, const uint8_
     d.phys = cp.phys; d.flba = cp.flba; d.width = cp.width; d.narrow = cp.narrow;
   }
   QHIP_HIP_CHECK(hipMemcpyAsync(cols_d.ptr, desc.data(), ncols * sizeof(qh_pq_col), hipMemcpyHostToDevice, ctx->stream));
+  DevBuf unpack_d;
+  if (nunpack) unpack_d.alloc((size_t)nunpack * sizeof(qh_pq_unpack));
+  if (nunpack) QHIP_HIP_CHECK(hipMemcpyAsync(unpack_d.ptr, plan.unpack.data(), (size_t)nunpack * sizeof(qh_pq_unpack), hipMemcpyHostToDevice, ctx->stream));
   mark(1);
 
-  // ---- 2 .. 4: levels, string walk, values
+  // ---- level 2: the Snappy pages into their slots
   time_mark(ctx, 2);
+  if (nunpack) {
+    launch_pq_unsnap(file.as<uint8_t>(), buf_bytes, unpack_d.as<qh_pq_unpack>(), nunpack, st_dev + kUnpackWord, nullptr, ctx->stream);
+    mark(6);
+  }
+
+  // ---- 2 .. 4: levels, string walk, values
   launch_pq_levels(file.as<uint8_t>(), pages_d.as<qh_pq_page>(), npages, cols_d.as<qh_pq_col>(), state_d.as<qh_pq_state>(), st_dev, st_dev + 1, ctx->stream);
   mark(2);
-  launch_pq_strings(file.as<uint8_t>(), plan.upload_bytes, pages_d.as<qh_pq_page>(), npages, cols_d.as<qh_pq_col>(), state_d.as<qh_pq_state>(), st_dev, ctx->stream);
+  launch_pq_strings(file.as<uint8_t>(), buf_bytes, pages_d.as<qh_pq_page>(), npages, cols_d.as<qh_pq_col>(), state_d.as<qh_pq_state>(), st_dev, ctx->stream);
   mark(3);
   launch_pq_values(file.as<uint8_t>(), pages_d.as<qh_pq_page>(), npages, cols_d.as<qh_pq_col>(), state_d.as<qh_pq_state>(), st_dev, st_dev + 1 + QH_PQ_MAX_COLS, ctx->stream);
   time_mark(ctx, 3);
   mark(4);
   std::vector<uint64_t> back(st_host.size());
   copy_sync(ctx->stream, back.data(), st.ptr, st.bytes, hipMemcpyDeviceToHost);   // the host wait (also: the upload has left `bytes`)
-  if (back[0] != ~0ULL) {
-    const uint64_t pg = back[0] >> 8;
-    qhip_pq::PqNeedsHost e{(int)(back[0] & 0xFF), -1, -1, -1};
+  // (a page whose unpacking failed holds whatever its slot held: what the later passes say of it does not count)
+  const uint64_t offender = back[kUnpackWord] != ~0ULL ? back[kUnpackWord] : back[0];
+  if (offender != ~0ULL) {
+    const uint64_t pg = offender >> 8;
+    qhip_pq::PqNeedsHost e{(int)(offender & 0xFF), -1, -1, -1};
     if (pg < plan.where.size()) { e.row_group = plan.where[pg].row_group; e.column = plan.where[pg].column; e.page = plan.where[pg].page; }
     fail(QHIP_UNSUPPORTED, qhip_pq::needs_host_text(e));
   }
@@ -178,6 +199,10 @@ qhip_table* table_from_parquet(Ctx* ctx, const ArrowSchema* schema, const uint8_
   if (ctx->timing) {
     QHIP_HIP_CHECK(sync_event(ev[5]));
     for (int k = 0; k < 5; ++k) (void)hipEventElapsedTime(&ctx->parquet_pass_ms[k], ev[k], ev[k + 1]);
+    if (ev[6]) {   // "levels" begins behind the unpack pass, "upload" stays the upload
+      (void)hipEventElapsedTime(&ctx->parquet_unpack_ms, ev[1], ev[6]);
+      (void)hipEventElapsedTime(&ctx->parquet_pass_ms[1], ev[6], ev[2]);
+    }
   }
   time_mark(ctx, 1);
   t->num_rows = (int64_t)R;
@@ -192,6 +217,60 @@ qhip_table* table_from_parquet(Ctx* ctx, const ArrowSchema* schema, const uint8_
   ctx->stats.bytes_per_row_read = (double)plan.upload_bytes / (double)R;
   snprintf(ctx->stats.main_kernel_name, sizeof ctx->stats.main_kernel_name, "k_pq_values");
   return t.release();
+}
+
+// qhip_snappy_decode: k_pq_unsnap over raw streams, with the checks the page walk makes of a page's sizes. A refused stream is
+// an answer (status), not an error.
+void snappy_decode(Ctx* ctx, const uint8_t* bytes, int64_t n_bytes, const int64_t* src_offsets, const int64_t* dst_sizes, int64_t n_streams, uint8_t* out,
+                   int64_t out_bytes, int32_t* status) {
+  uint64_t total_out = 0;
+  for (int64_t k = 0; k < n_streams; ++k) {
+    const int64_t a = src_offsets[k], b = src_offsets[k + 1];
+    if (a < 0 || b < a || b > n_bytes || b - a > 0x7FFFFFFF || dst_sizes[k] < 0 || dst_sizes[k] > 0x7FFFFFFF)
+      fail(QHIP_INVALID_ARGUMENT, "qhip_snappy_decode: stream " + std::to_string(k) + " lies outside the bytes, or a size is negative or above 2^31 - 1");
+    total_out += (uint64_t)dst_sizes[k];
+  }
+  if (total_out > (uint64_t)out_bytes) fail(QHIP_INVALID_ARGUMENT, "qhip_snappy_decode: out is smaller than the sum of dst_sizes");
+  const uint64_t base = ((uint64_t)n_bytes + 15) & ~(uint64_t)15;
+  uint64_t area = 0;
+  std::vector<qh_pq_unpack> tab;
+  for (int64_t k = 0; k < n_streams; ++k) {
+    qh_pq_unpack u;
+    memset(&u, 0, sizeof u);
+    const int bad = qh_snap_check_sizes(bytes + src_offsets[k], (uint64_t)(src_offsets[k + 1] - src_offsets[k]), (uint64_t)dst_sizes[k], &u.start);
+    status[k] = bad ? QH_PQ_R_SNAPPY_BASE + bad : QH_PQ_OK;
+    if (bad) continue;
+    u.src = (uint64_t)src_offsets[k]; u.src_size = (uint32_t)(src_offsets[k + 1] - src_offsets[k]);
+    u.dst = base + area; u.dst_size = (uint32_t)dst_sizes[k];
+    u.page = (uint32_t)k;
+    tab.push_back(u);
+    area += ((uint64_t)u.dst_size + 15) & ~(uint64_t)15;
+  }
+  ctx->parquet_unpack_ms = 0;
+  if (tab.empty()) return;
+  QHIP_HIP_CHECK(hipSetDevice(ctx->device));
+  const uint32_t nt = (uint32_t)tab.size();
+  DevBuf buf((size_t)(base + area)), tab_d((size_t)nt * sizeof(qh_pq_unpack)), st_d((size_t)nt * 4);
+  if (n_bytes) QHIP_HIP_CHECK(hipMemcpyAsync(buf.ptr, bytes, (size_t)n_bytes, hipMemcpyHostToDevice, ctx->stream));
+  QHIP_HIP_CHECK(hipMemcpyAsync(tab_d.ptr, tab.data(), (size_t)nt * sizeof(qh_pq_unpack), hipMemcpyHostToDevice, ctx->stream));
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int k = 0; k < 2; ++k) if (e[k]) (void)hipEventDestroy(e[k]); } } ev_guard{ev};
+  if (ctx->timing) { QHIP_HIP_CHECK(hipEventCreate(&ev[0])); QHIP_HIP_CHECK(hipEventCreate(&ev[1])); QHIP_HIP_CHECK(hipEventRecord(ev[0], ctx->stream)); }
+  launch_pq_unsnap(buf.as<uint8_t>(), base + area, tab_d.as<qh_pq_unpack>(), nt, nullptr, st_d.as<uint32_t>(), ctx->stream);
+  if (ctx->timing) QHIP_HIP_CHECK(hipEventRecord(ev[1], ctx->stream));
+  std::vector<uint8_t> unpacked((size_t)area);
+  std::vector<uint32_t> st(nt);
+  if (area) QHIP_HIP_CHECK(hipMemcpyAsync(unpacked.data(), (const uint8_t*)buf.ptr + base, (size_t)area, hipMemcpyDeviceToHost, ctx->stream));
+  copy_sync(ctx->stream, st.data(), st_d.ptr, (size_t)nt * 4, hipMemcpyDeviceToHost);
+  if (ctx->timing) (void)hipEventElapsedTime(&ctx->parquet_unpack_ms, ev[0], ev[1]);
+  std::vector<uint64_t> out_at((size_t)n_streams);
+  uint64_t at = 0;
+  for (int64_t k = 0; k < n_streams; ++k) { out_at[(size_t)k] = at; at += (uint64_t)dst_sizes[k]; }
+  for (uint32_t i = 0; i < nt; ++i) {
+    const qh_pq_unpack& u = tab[i];
+    status[u.page] = st[i] ? (int32_t)(QH_PQ_R_SNAPPY_BASE + st[i]) : QH_PQ_OK;
+    if (!st[i] && u.dst_size) memcpy(out + out_at[u.page], unpacked.data() + (u.dst - base), u.dst_size);
+  }
 }
 
 }  // namespace qhip
@@ -211,6 +290,20 @@ int qhip_ctx_parquet_pass_ms(const qhip_ctx* ctx, double* out, int32_t n_out) {
   if (!ctx || !out || n_out != 5) return QHIP_INVALID_ARGUMENT;
   for (int k = 0; k < 5; ++k) out[k] = (double)ctx->parquet_pass_ms[k];
   return QHIP_OK;
+}
+
+int qhip_ctx_parquet_unpack_ms(const qhip_ctx* ctx, double* out) {
+  if (!ctx || !out) return QHIP_INVALID_ARGUMENT;
+  *out = (double)ctx->parquet_unpack_ms;
+  return QHIP_OK;
+}
+
+int qhip_snappy_decode(qhip_ctx* ctx, const void* bytes, int64_t n_bytes, const int64_t* src_offsets, const int64_t* dst_sizes, int64_t n_streams, void* out,
+                       int64_t out_bytes, int32_t* status) {
+  if (!ctx || n_bytes < 0 || (n_bytes > 0 && !bytes) || n_streams < 0 || out_bytes < 0 || (out_bytes > 0 && !out)) return QHIP_INVALID_ARGUMENT;
+  if (n_streams > 0 && (!src_offsets || !dst_sizes || !status)) return QHIP_INVALID_ARGUMENT;
+  if (n_streams >= (1 << 24)) return QHIP_INVALID_ARGUMENT;
+  return guarded(ctx, [&] { snappy_decode(ctx, (const uint8_t*)bytes, n_bytes, src_offsets, dst_sizes, n_streams, (uint8_t*)out, out_bytes, status); });
 }
 
 }  // extern "C"

@@ -1,7 +1,8 @@
 // parquet_meta.hpp — the host half of the device Parquet decoder that needs no device (parquet.cpp includes it; so does
 // tests/cpp/parquet_tests.cpp, which runs it under the sanitizers): a bounds-checked Thrift compact-protocol reader, the footer
 // (FileMetaData) and page headers decoded as far as they are used, the match of a column's physical type and annotation against
-// its Arrow type, and the page walk that turns the projected chunks into a page table. Plain C++, no Arrow, no HIP.
+// its Arrow type, and the page walk that turns the projected chunks into a page table and, at format level 2, the pages of Snappy
+// chunks into an unpack table with their slots in the unpack area. Plain C++, no Arrow, no HIP.
 // Every offset, length and count comes from the file and is checked before it is followed: a violation throws PqNeedsHost.
 #pragma once
 #include <cstdint>
@@ -11,6 +12,11 @@
 
 #include "qhip.h"
 #include "device/qhip_parquet.inc"
+#include "device/qhip_snappy.inc"
+
+static_assert(QH_PQ_R_SNAPPY_PREAMBLE == QH_PQ_R_SNAPPY_BASE + QH_SNAP_E_PREAMBLE && QH_PQ_R_SNAPPY_OFFSET == QH_PQ_R_SNAPPY_BASE + QH_SNAP_E_OFFSET &&
+                  QH_PQ_R_COUNT == QH_PQ_R_SNAPPY_BASE + QH_SNAP_E_COUNT,
+              "the Snappy reasons follow the decoder's error codes");
 
 namespace qhip_pq {
 
@@ -112,6 +118,7 @@ struct Thrift {
 enum { PT_BOOLEAN = 0, PT_INT32 = 1, PT_INT64 = 2, PT_INT96 = 3, PT_FLOAT = 4, PT_DOUBLE = 5, PT_BYTE_ARRAY = 6, PT_FLBA = 7 };
 enum { ENC_PLAIN = 0, ENC_PLAIN_DICTIONARY = 2, ENC_RLE = 3, ENC_BIT_PACKED = 4, ENC_RLE_DICTIONARY = 8 };
 enum { PAGE_DATA = 0, PAGE_INDEX = 1, PAGE_DICTIONARY = 2, PAGE_DATA_V2 = 3 };
+enum { CODEC_UNCOMPRESSED = 0, CODEC_SNAPPY = 1 };
 enum { L_NONE = 0, L_STRING, L_DECIMAL, L_DATE, L_TIMESTAMP, L_INT, L_OTHER };
 
 struct SchemaElem {
@@ -328,11 +335,17 @@ struct Plan {
   std::vector<Range> ranges;          // the projected chunks, one behind the other in the upload buffer
   std::vector<qh_pq_page> pages;      // (`col`: index into cols; positions in the upload buffer)
   std::vector<PageWhere> where;       // for the message: what pages[k] is in the file
+  // format level 2: the pages of the Snappy chunks. The device buffer is the uploaded chunks, then (16-byte aligned, at
+  // unpack_base) the unpack area: one 16-byte aligned slot of uncompressed_page_size bytes per entry. Empty at level 1.
+  std::vector<qh_pq_unpack> unpack;
+  uint64_t unpack_base = 0, unpack_bytes = 0;
+  uint64_t buffer_bytes() const { return unpack.empty() ? upload_bytes : unpack_base + unpack_bytes; }
 };
 
 // names: the schema's field names (checked against the file's when given). types: the Arrow type of EVERY field. proj: the
-// fields to decode, in output order.
-inline Plan plan_file(const uint8_t* file, uint64_t n, const std::vector<std::string>* names, const std::vector<ArrowType>& types, const std::vector<int32_t>& proj) {
+// fields to decode, in output order. level: the format level (qhip_ctx_set_parquet_format); 2 admits SNAPPY chunks.
+inline Plan plan_file(const uint8_t* file, uint64_t n, const std::vector<std::string>* names, const std::vector<ArrowType>& types, const std::vector<int32_t>& proj,
+                      int level = 1) {
   if (n >= 4 && memcmp(file, "PARE", 4) == 0) needs_host(QH_PQ_R_ENCRYPTED);
   if (n >= 4 && memcmp(file + n - 4, "PARE", 4) == 0) needs_host(QH_PQ_R_ENCRYPTED);
   if (n < 12 || memcmp(file, "PAR1", 4) != 0 || memcmp(file + n - 4, "PAR1", 4) != 0) needs_host(QH_PQ_R_MAGIC);
@@ -376,6 +389,7 @@ inline Plan plan_file(const uint8_t* file, uint64_t n, const std::vector<std::st
   plan.num_rows = rows;
 
   // ---- the page walk: one header per page of every projected chunk
+  std::vector<uint8_t> in_unpack;   // per page: 1 its pos, 2 its dict_pos is relative to the unpack area
   uint64_t first_row = 0;
   for (size_t gi = 0; gi < f.groups.size(); ++gi) {
     const RowGroup& g = f.groups[gi];
@@ -387,7 +401,8 @@ inline Plan plan_file(const uint8_t* file, uint64_t n, const std::vector<std::st
       const int64_t G = (int64_t)gi, C = proj[k];
       if (ch.has_file_path) needs_host(QH_PQ_R_FILE_PATH, G, C);
       if (!ch.has_meta || ch.type != f.schema[(size_t)proj[k] + 1].type) needs_host(QH_PQ_R_CORRUPT, G, C);
-      if (ch.codec != 0) needs_host(QH_PQ_R_CODEC, G, C);
+      const bool snappy = level >= 2 && ch.codec == CODEC_SNAPPY;
+      if (ch.codec != CODEC_UNCOMPRESSED && !snappy) needs_host(QH_PQ_R_CODEC, G, C);
       const int64_t start = ch.dict_off > 0 ? ch.dict_off : ch.data_off;
       if (start < 4 || ch.total_compressed < 0 || (uint64_t)start > fstart || (uint64_t)ch.total_compressed > fstart - (uint64_t)start) needs_host(QH_PQ_R_CORRUPT, G, C);
       const uint64_t cbytes = (uint64_t)ch.total_compressed, cbuf = plan.upload_bytes;
@@ -403,12 +418,30 @@ inline Plan plan_file(const uint8_t* file, uint64_t n, const std::vector<std::st
         PageHeader h;
         try { h = read_page_header(chunk + pos, cbytes - pos); } catch (const PqNeedsHost& e) { needs_host(e.reason, G, C, pageno); }
         const uint64_t payload = pos + h.header_bytes;
-        if (h.compressed < 0 || h.compressed != h.uncompressed || (uint64_t)h.compressed > cbytes - payload || h.compressed > 0x7FFFFFFF)
+        if (h.compressed < 0 || (!snappy && h.compressed != h.uncompressed) || (uint64_t)h.compressed > cbytes - payload || h.compressed > 0x7FFFFFFF)
           needs_host(QH_PQ_R_CORRUPT, G, C, pageno);
-        const uint32_t size = (uint32_t)h.compressed;
+        uint32_t size = (uint32_t)h.compressed;   // of the page as the device's passes see it
         qh_pq_page pg;
         memset(&pg, 0, sizeof pg);
-        pg.pos = cbuf + payload; pg.size = size; pg.col = (uint32_t)k;
+        pg.pos = cbuf + payload; pg.col = (uint32_t)k;
+        if (snappy) {
+          // the page is unpacked into a slot of the unpack area first: pos is relative to that area until the upload's size is
+          // final (below). The sizes are the file's claims: nothing is reserved for a claim the stream cannot keep.
+          if (h.type == PAGE_DATA_V2) needs_host(QH_PQ_R_PAGE_V2, G, C, pageno);   // (its levels lie outside the compressed part)
+          if (h.uncompressed < 0 || h.uncompressed > 0x7FFFFFFF) needs_host(QH_PQ_R_CORRUPT, G, C, pageno);
+          qh_pq_unpack u;
+          memset(&u, 0, sizeof u);
+          const int bad = qh_snap_check_sizes(chunk + payload, (uint64_t)h.compressed, (uint64_t)h.uncompressed, &u.start);
+          if (bad) needs_host(QH_PQ_R_SNAPPY_BASE + bad, G, C, pageno);
+          u.src = cbuf + payload; u.src_size = (uint32_t)h.compressed;
+          u.dst = plan.unpack_bytes; u.dst_size = (uint32_t)h.uncompressed;
+          u.page = (uint32_t)plan.pages.size();
+          plan.unpack.push_back(u);
+          plan.unpack_bytes += ((uint64_t)u.dst_size + 15) & ~(uint64_t)15;
+          pg.pos = u.dst;
+          size = u.dst_size;
+        }
+        pg.size = size;
         if (h.type == PAGE_DICTIONARY) {
           if (have_dict || seen_data) needs_host(QH_PQ_R_PAGE_ORDER, G, C, pageno);
           if (!h.has_dict || h.num_values < 0 || h.num_values > 0x7FFFFFFF) needs_host(QH_PQ_R_CORRUPT, G, C, pageno);
@@ -439,12 +472,22 @@ inline Plan plan_file(const uint8_t* file, uint64_t n, const std::vector<std::st
         else if (h.type == PAGE_INDEX) needs_host(QH_PQ_R_INDEX_PAGE, G, C, pageno);
         else needs_host(QH_PQ_R_PAGE_ORDER, G, C, pageno);
         plan.pages.push_back(pg);
+        in_unpack.push_back(snappy ? (uint8_t)(1 | (h.type == PAGE_DATA && have_dict ? 2 : 0)) : (uint8_t)0);
         plan.where.push_back(PageWhere{G, C, pageno});
         if (plan.pages.size() >= (1u << 24)) needs_host(QH_PQ_R_CORRUPT, G, C, pageno);   // (the device's error word keeps 8 bits for the reason)
-        pos = payload + size;
+        pos = payload + (uint64_t)h.compressed;
       }
     }
     first_row += (uint64_t)g.num_rows;
+  }
+  // ---- the unpack area begins behind the last uploaded chunk: now its slots have their place in the buffer
+  if (!plan.unpack.empty()) {
+    plan.unpack_base = (plan.upload_bytes + 15) & ~(uint64_t)15;
+    for (qh_pq_unpack& u : plan.unpack) u.dst += plan.unpack_base;
+    for (size_t p = 0; p < plan.pages.size(); ++p) {
+      if (in_unpack[p] & 1) plan.pages[p].pos += plan.unpack_base;
+      if (in_unpack[p] & 2) plan.pages[p].dict_pos += plan.unpack_base;
+    }
   }
   return plan;
 }

@@ -172,10 +172,11 @@ def read_parquet(path: str, columns: Optional[Sequence[str]] = None, batch_rows:
 
     device=True (None: the environment's QHIP_PARQUET_DEVICE, default 0): the footer and one header per page are read on the
     host, the bytes of the projected column chunks alone cross PCIe and the pages are decoded on the device
-    (qhip_table_from_parquet); the result's `decoded_on_device` is True. The device decodes format level 1:
-    UNCOMPRESSED chunks — write with `compression="NONE"`; pyarrow's default, Snappy, takes the host path — data pages V1, PLAIN
-    and dictionary encodings, flat columns. Every other file falls back silently to the host read below, which also produces
-    every error message."""
+    (qhip_table_from_parquet); the result's `decoded_on_device` is True. What the device decodes is the context's
+    format level (`Context.set_parquet_format` / QHIP_PARQUET_FORMAT). Level 1, the default: UNCOMPRESSED chunks — write with
+    `compression="NONE"`; pyarrow's default, Snappy, takes the host path — data pages V1, PLAIN and dictionary encodings, flat
+    columns. Level 2 also decodes SNAPPY chunks, unpacked on the device; zstd, gzip, lz4 and brotli still take the host path.
+    Every other file falls back silently to the host read below, which also produces every error message."""
     import os
     import pyarrow.parquet as pq
     if device is None:

@@ -13,7 +13,13 @@ median of --runs calls after --warmup calls, each ending in a device synchronise
 
 (a) .. (c) alternate in one process, --repeat times. --columns a,b,c reads a projection: the other columns' chunks stay on disk.
 
+--compression snappy writes the same rows with pyarrow's defaults (Snappy) and sets format level 2 (Context.set_parquet_format),
+without which such a file takes the host path. (d) then also has the unpack pass (k_pq_unsnap, between the upload and
+k_pq_levels) with the GB/s of uncompressed bytes it produces, and the header line says how many bytes the projected chunks have
+compressed and uncompressed; (c) copies the compressed bytes, which are what crosses PCIe.
+
     python tools/parquet_decode_timing.py [--gb 1.0] [--runs 10] [--warmup 2] [--repeat 2] [--threads 16] [--columns l_quantity,l_shipdate]
+                                          [--compression none|snappy]
 """
 import argparse
 import ctypes as C
@@ -37,13 +43,23 @@ from qurious_amd._ffi import DeviceTable  # noqa: E402
 PASSES = ["upload", "k_pq_levels", "k_pq_strings", "k_pq_values", "Utf8 offsets + k_csv_copy_utf8"]
 
 
-def write_file(path, target_bytes):
-    """lineitem rows, one row group per 2^20 of them, until the file has about target_bytes; returns the row count"""
+def write_file(path, target_bytes, compression="none"):
+    """lineitem rows, one row group per 2^20 of them, until the file has about target_bytes; returns the row count.
+    compression="snappy": the rows the uncompressed file would have, written with pyarrow's defaults"""
     step, rows = 1 << 20, 0
     schema = pa.schema([pa.field(f.name, f.type) for f in synth.LINEITEM_SCHEMA])
+    group = lambda first: pa.Table.from_batches([synth.lineitem_batch(first, step)]).cast(schema)   # noqa: E731
+    if compression == "snappy":
+        pq.write_table(group(0), path + ".one", compression="NONE", row_group_size=step)
+        groups = -(-target_bytes // os.path.getsize(path + ".one"))
+        os.remove(path + ".one")
+        with pq.ParquetWriter(path, schema) as w:
+            for g in range(groups):
+                w.write_table(group(g * step), row_group_size=step)
+        return groups * step
     with pq.ParquetWriter(path, schema, compression="NONE") as w:
         while True:
-            w.write_table(pa.Table.from_batches([synth.lineitem_batch(rows, step)]).cast(schema), row_group_size=step)
+            w.write_table(group(rows), row_group_size=step)
             rows += step
             if os.path.getsize(path) >= target_bytes:
                 return rows
@@ -68,22 +84,26 @@ def main():
     ap.add_argument("--repeat", type=int, default=2)
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--columns", type=str, default="", help="comma-separated projection (default: every column)")
+    ap.add_argument("--compression", choices=["none", "snappy"], default="none", help="snappy: pyarrow's defaults, decoded at format level 2")
     args = ap.parse_args()
     pa.set_cpu_count(args.threads)
     columns = [c for c in args.columns.split(",") if c] or None
     ctx = q.get_context()
+    if args.compression == "snappy":
+        ctx.set_parquet_format(2)
     hip = C.CDLL(None)   # (libqhip.so is loaded globally and brings the HIP runtime with it)
     hip.hipMalloc.argtypes, hip.hipMemcpy.argtypes, hip.hipFree.argtypes = [C.POINTER(C.c_void_p), C.c_size_t], [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int], [C.c_void_p]
     with tempfile.TemporaryDirectory() as d:
         path = os.path.join(d, "lineitem.parquet")
-        rows = write_file(path, int(args.gb * 1e9))
+        rows = write_file(path, int(args.gb * 1e9), args.compression)
         nbytes = os.path.getsize(path)
         md = pq.ParquetFile(path).metadata
         names = md.schema.names
         want = set(columns) if columns else set(names)
         chunk_bytes = sum(md.row_group(g).column(c).total_compressed_size for g in range(md.num_row_groups) for c in range(md.num_columns) if names[c] in want)
+        plain_bytes = sum(md.row_group(g).column(c).total_uncompressed_size for g in range(md.num_row_groups) for c in range(md.num_columns) if names[c] in want)
         print(f"device {ctx.device_name()}; {path}: {nbytes} bytes, {rows} rows in {md.num_row_groups} row groups, columns {sorted(want)}: {chunk_bytes} bytes of "
-              f"projected chunks; median (min) of {args.runs} calls after {args.warmup} warm-up calls; host read with {args.threads} threads", flush=True)
+              f"projected chunks ({args.compression}; {plain_bytes} bytes uncompressed); median (min) of {args.runs} calls after {args.warmup} warm-up calls; host read with {args.threads} threads", flush=True)
 
         def host_path():
             t = datasource.read_parquet(path, columns, device=False)
@@ -115,7 +135,7 @@ def main():
         per = []
         for _ in range(args.warmup + args.runs):
             device_path()
-            per.append(ctx.parquet_pass_ms())
+            per.append(ctx.parquet_pass_ms() + [ctx.parquet_unpack_ms()])
         ctx.set_timing(False)
         per = per[args.warmup:]
         kernels = 0.0
@@ -123,6 +143,10 @@ def main():
             med = statistics.median(p[k] for p in per)
             kernels += med if k else 0.0
             print(f"(d) {name:32s} {med:9.3f} ms  {chunk_bytes / max(med, 1e-6) / 1e6:9.1f} GB/s of chunk bytes", flush=True)
+            if k == 0 and args.compression == "snappy":
+                med = statistics.median(p[5] for p in per)
+                kernels += med
+                print(f"(d) {'k_pq_unsnap (unpack)':32s} {med:9.3f} ms  {plain_bytes / max(med, 1e-6) / 1e6:9.1f} GB/s of uncompressed bytes", flush=True)
         print(f"(d) kernels together (all but the upload) {kernels:9.3f} ms  {chunk_bytes / max(kernels, 1e-6) / 1e6:9.1f} GB/s of chunk bytes", flush=True)
         del src
         m.close()
