@@ -293,6 +293,7 @@ static int eval_cast(const qo_col* in, qhip_dtype to, int64_t n, qo_col* out) {
     if (is_float(to.id)) {
       double f;
       if (from.id == QHIP_DECIMAL128) f = (double)get_int(in, i) / pow(10.0, from.scale);
+      else if (to.id == QHIP_FLOAT32 && !is_float(from.id)) { ((float*)out->values)[i] = (float)get_int(in, i); continue; }   /* one rounding, not two through double */
       else f = get_f64(in, i);
       if (to.id == QHIP_FLOAT32) ((float*)out->values)[i] = (float)f; else ((double*)out->values)[i] = f;
       continue;
@@ -324,6 +325,7 @@ static int eval_cast(const qo_col* in, qhip_dtype to, int64_t n, qo_col* out) {
       if (is_float(from.id)) {
         double t = trunc(get_f64(in, i));
         i128 lo, hi; int_limits(to.id, &lo, &hi);
+        /* ((double)hi rounds up to 2^63 / 2^64 for the 64-bit types: those two values pass here and fail the range check on v below) */
         if (!(t >= (double)lo && t <= (double)hi)) QO_FAIL(QHIP_EXEC_ERROR, "Cast error: Can't cast value to type %d", to.id);
         v = (i128)t;
       } else if (from.id == QHIP_DECIMAL128) {

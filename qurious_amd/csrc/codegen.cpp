@@ -310,6 +310,7 @@ static void emit_agg_eval(std::ostringstream& s, ExprGen& g, const ExprSet& es, 
   if (predicate_root >= 0) {
     g.emit(predicate_root, ev);
     ev += "    r.pass = " + pass_expr(g, predicate_root) + ";\n";
+    g.set_err_gate("r.pass");   // keys and arguments raise only for rows the fused filter passes (the predicate itself: every row)
   } else {
     ev += "    r.pass = true;\n";
   }
@@ -541,7 +542,10 @@ void plan_keys(const ExprSet& es, const std::vector<InputCol>& input, const int3
   // scan filter fused into the key evaluation: a row the predicate rejects gets an invalid key, i.e. it is never
   // inserted into / probed against the join table — the filtered batch is never materialised
   check_predicate(es, predicate_root);
-  if (predicate_root >= 0) g.emit(predicate_root, code);
+  if (predicate_root >= 0) {
+    g.emit(predicate_root, code);
+    g.set_err_gate(pass_expr(g, predicate_root));   // key expressions raise only for rows the fused scan filter passes
+  }
   emit_key_words(g, es, out.keys, false, "k", code, &all);
   const std::string key_all = all;   // (the keys alone, before a fused scan filter joins in)
   const std::string pass = predicate_root >= 0 ? "(" + pass_expr(g, predicate_root) + ")" : std::string("true");

@@ -54,6 +54,12 @@ class ExprGen {
   // multiply-add chain per column), raw mode, and the bytes of plain Utf8 key columns fetched with the row's other loads
   void use_tile_loads(const std::vector<KeyDesc>& keys);
   std::string raw_fields, load_code;
+  // error flags under a fused filter: the reference filters first and evaluates keys and arguments on the surviving rows only,
+  // so what is emitted after set_err_gate(cond) raises its flags (Divide by zero, Arithmetic overflow, Cast error) only where
+  // `cond` — the filter's pass expression — holds. The predicate's own nodes are emitted before the gate is set: the reference
+  // evaluates the predicate on every row. Text without a fallible node is the same with and without a gate.
+  void set_err_gate(const std::string& cond) { gate_ = cond; }
+  bool raises() const { return raises_; }   // whether any emitted node can raise a flag
   static std::string ctype(const DType& t);
   static std::string i128_const(i128 v);
 
@@ -61,6 +67,7 @@ class ExprGen {
   int col_slot(int table_col);
   int lit_slot(const ENode& n);
   int str_slot(const std::string& bytes);   // a literal slot holding only string bytes (LIKE patterns)
+  std::string raise(unsigned bits);         // the statement `err |= bits` (under the gate, if one is set)
   // one per node kind (exprgen.cpp): the node's children go to `out` first, its own statements to `o`
   void emit_column(int k, const ENode& n, std::ostringstream& o);
   void emit_utf8_column(int k, const ENode& n, const std::string& S, std::ostringstream& ld, std::ostringstream& o);
@@ -84,6 +91,8 @@ class ExprGen {
   std::string base_ = "", idx_ = "i", row_ = "i";
   bool raw_ = false;
   bool nt_ = false;
+  std::string gate_;
+  bool raises_ = false;
   std::map<int, int> utf8_key_words_;
 };
 

@@ -70,6 +70,13 @@ static std::string i128_str(i128 v) {
   return neg ? "-" + s : s;
 }
 
+// whether v * 10^k is a Decimal128 of precision p: |v| < 10^(p - k), decided on v (the product may not fit an i128)
+static bool scaled_fits(i128 v, int k, int p) {
+  if (p <= k) return v == 0;
+  const i128 lim = pow10_i128(p - k);
+  return v < lim && v > -lim;
+}
+
 void fold_literal_cast(const ENode& src, const DType& to, ENode& out) {
   out = ENode();
   out.kind = QHIP_EXPR_LITERAL;
@@ -112,13 +119,11 @@ void fold_literal_cast(const ENode& src, const DType& to, ENode& out) {
       if (v < lo || v > hi) overflow(i128_str(v));
       out.lo = (uint64_t)(u128)v; out.hi = v < 0 ? -1 : 0; return;
     }
-    if (dtype_is_float(to)) { out.f = to.id == QHIP_FLOAT32 ? (double)(float)(double)v : (double)v; return; }
+    if (dtype_is_float(to)) { out.f = to.id == QHIP_FLOAT32 ? (double)(float)v : (double)v; return; }   // (one rounding, like the kernels)
     if (to.id == QHIP_DECIMAL128) {
       if (to.scale < 0) fail(QHIP_UNSUPPORTED, "negative decimal scale");
-      i128 r = v * pow10_i128(to.scale);
-      i128 lim = pow10_i128(to.precision);
-      if (r >= lim || r <= -lim) overflow(i128_str(v));
-      set_i128(out, r); return;
+      if (!scaled_fits(v, to.scale, to.precision)) overflow(i128_str(v));
+      set_i128(out, v * pow10_i128(to.scale)); return;
     }
     if (to.id == QHIP_BOOL) { out.lo = v != 0; return; }
     fail(QHIP_UNSUPPORTED, "literal cast " + dtype_name(from) + " -> " + dtype_name(to));
@@ -129,7 +134,7 @@ void fold_literal_cast(const ENode& src, const DType& to, ENode& out) {
     if (is_intlike(to)) {
       i128 lo, hi; int_range(to, lo, hi);
       double tv = std::trunc(v);
-      if (!(tv >= (double)lo && tv <= (double)hi)) overflow(std::to_string(v));
+      if (!(tv >= (double)lo && tv < (double)(hi + 1))) overflow(std::to_string(v));   // (hi + 1 = 2^bits is exact; (double)hi is not)
       i128 r = (i128)tv;
       out.lo = (uint64_t)(u128)r; out.hi = r < 0 ? -1 : 0; return;
     }
@@ -147,8 +152,10 @@ void fold_literal_cast(const ENode& src, const DType& to, ENode& out) {
     i128 v = lit_i128(src);
     if (to.id == QHIP_DECIMAL128) {
       i128 r;
-      if (to.scale >= from.scale) r = v * pow10_i128(to.scale - from.scale);
-      else {
+      if (to.scale >= from.scale) {
+        if (!scaled_fits(v, to.scale - from.scale, to.precision)) overflow(i128_str(v));
+        r = v * pow10_i128(to.scale - from.scale);
+      } else {
         i128 d = pow10_i128(from.scale - to.scale), q = v / d, rem = v % d, half = d / 2;
         if (rem >= half + (d & 1 ? 1 : 0) || (rem >= half && !(d & 1))) q += 1;
         else if (-rem >= half + (d & 1 ? 1 : 0) || (-rem >= half && !(d & 1))) q -= 1;

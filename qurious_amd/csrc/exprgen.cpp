@@ -76,6 +76,13 @@ void ExprGen::use_tile_loads(const std::vector<KeyDesc>& keys) {
     if (kd.type.id == QHIP_UTF8 && es_.at(kd.root).kind == QHIP_EXPR_COLUMN) mark_utf8_key(kd.root, kd.words);
 }
 
+// the statement that raises status bit(s) `bits`: under the gate, if one is set (codegen.hpp: set_err_gate)
+std::string ExprGen::raise(unsigned bits) {
+  raises_ = true;
+  const std::string st = "err |= " + std::to_string(bits) + "u;";
+  return gate_.empty() ? st : "{ if (" + gate_ + ") " + st + " }";
+}
+
 std::string ExprGen::ok(int k) const { return es_.at(k).nullable ? "n" + std::to_string(k) : "true"; }
 
 int ExprGen::col_slot(int table_col) {
@@ -358,10 +365,10 @@ void ExprGen::emit_int_arith(int k, const ENode& n, std::ostringstream& o) {
   // arrow `div`/`rem` are checked: DivideByZero, and MIN / -1 overflows (evaluated on valid rows only)
   o << "    " << T << " " << v << " = 0;\n";
   o << "    if (" << ok(k) << ") {\n";
-  o << "      if (" << rv << " == 0) err |= " << (1u << QS_DIV_ZERO) << "u;\n";
+  o << "      if (" << rv << " == 0) " << raise(1u << QS_DIV_ZERO) << "\n";
   if (signed_intlike(n.type)) {
     if (n.op == QHIP_OP_DIV)
-      o << "      else if (" << lv << " == " << int_min(n.type) << " && " << rv << " == -1) err |= " << (1u << QS_ARITH_OVERFLOW) << "u;\n";
+      o << "      else if (" << lv << " == " << int_min(n.type) << " && " << rv << " == -1) " << raise(1u << QS_ARITH_OVERFLOW) << "\n";
     else
       o << "      else if (" << rv << " == -1) " << v << " = 0;\n";
   }
@@ -377,9 +384,16 @@ void ExprGen::emit_cast(int k, const ENode& n, std::string& out, std::ostringstr
   const std::string T = ctype(to);
   if (n.nullable) o << "    const bool n" << K << " = " << ok(n.left) << ";\n";
   auto flag = [&](const std::string& cond) {
-    o << "    if (" << ok(k) << " && (" << cond << ")) err |= " << (1u << QS_CAST_OVERFLOW) << "u;\n";
+    o << "    if (" << ok(k) << " && (" << cond << ")) " << raise(1u << QS_CAST_OVERFLOW) << "\n";
   };
   auto flag_precision = [&]() { const std::string lim = i128_const(pow10_i128(to.precision)); flag(v + " >= " + lim + " || " + v + " <= -" + lim); };
+  // x * 10^k as a Decimal128 of the target precision: arrow-rs multiplies checked and then checks the precision, and both hold
+  // exactly when |x| < 10^(precision - k) (x == 0 when precision <= k) — tested on x, so no wrapped product can pass
+  auto flag_scaled = [&](const std::string& x, int k10) {
+    if (to.precision <= k10) { flag(x + " != 0"); return; }
+    const std::string lim = i128_const(pow10_i128(to.precision - k10));
+    flag(x + " >= " + lim + " || " + x + " <= -" + lim);
+  };
   // range checks in i128 so that every (from, to) pair is handled uniformly
   const std::string wide = std::string(from.id == QHIP_UINT64 ? "(i128)(u128)" : "(i128)") + cv;
   const std::string lo128 = signed_intlike(to) ? "(i128)" + int_min(to) : "(i128)0";
@@ -399,20 +413,25 @@ void ExprGen::emit_cast(int k, const ENode& n, std::string& out, std::ostringstr
   } else if (dtype_is_float(from) && intlike(to)) {
     const std::string tr = "trunc((double)" + cv + ")";
     const std::string lo = signed_intlike(to) ? "(double)" + int_min(to) : "0.0";
-    flag("!(" + tr + " >= " + lo + " && " + tr + " <= (double)" + int_max(to) + ")");
+    // arrow-rs (num::cast): lo <= trunc(x) < 2^bits. The bound is written as the power of two itself: (double)INT64_MAX
+    // rounds up to 2^63, which `<=` would let through
+    static const char* const s2[] = {"128.0", "32768.0", "2147483648.0", "9223372036854775808.0"}, *const u2[] = {"256.0", "65536.0", "4294967296.0", "18446744073709551616.0"};
+    const std::string hi = (signed_intlike(to) ? s2 : u2)[log2u((uint32_t)dtype_width(to))];
+    flag("!(" + tr + " >= " + lo + " && " + tr + " < " + hi + ")");
     o << "    const " << T << " " << v << " = (" << T << ")" << tr << ";\n";
   } else if (intlike(from) && to.id == QHIP_DECIMAL128) {
-    o << "    const i128 " << v << " = " << wide << " * " << i128_const(pow10_i128(to.scale)) << ";\n";
-    flag_precision();
+    o << "    const i128 " << v << " = (i128)((u128)" << wide << " * (u128)" << i128_const(pow10_i128(to.scale)) << ");\n";
+    flag_scaled(wide, to.scale);
   } else if (from.id == QHIP_DECIMAL128 && to.id == QHIP_DECIMAL128) {
     if (to.scale >= from.scale) {
-      o << "    const i128 " << v << " = " << cv << " * " << i128_const(pow10_i128(to.scale - from.scale)) << ";\n";
+      o << "    const i128 " << v << " = (i128)((u128)" << cv << " * (u128)" << i128_const(pow10_i128(to.scale - from.scale)) << ");\n";
+      flag_scaled(cv, to.scale - from.scale);
     } else {
       const std::string d = i128_const(pow10_i128(from.scale - to.scale));
       o << "    i128 " << v << " = " << cv << " / " << d << "; { const i128 rm = " << cv << " % " << d << ", hf = " << d << " / 2;"
         << " if (rm >= hf) " << v << " += 1; else if (-rm >= hf) " << v << " -= 1; }\n";
+      flag_precision();
     }
-    flag_precision();
   } else if (from.id == QHIP_DECIMAL128 && dtype_is_float(to)) {
     char b[64]; snprintf(b, sizeof b, "1e%d", from.scale);
     o << "    const " << T << " " << v << " = (" << T << ")((double)" << cv << " / " << b << ");\n";
@@ -423,9 +442,12 @@ void ExprGen::emit_cast(int k, const ENode& n, std::string& out, std::ostringstr
   } else if (dtype_is_float(from) && to.id == QHIP_DECIMAL128) {
     char b[64]; snprintf(b, sizeof b, "1e%d", to.scale);
     o << "    const double f" << K << " = round((double)" << cv << " * " << b << ");\n";
-    char lim[64]; snprintf(lim, sizeof lim, "1e%d", to.precision);
-    flag("!(fabs(f" + K + ") < " + lim + ")");
-    o << "    const i128 " << v << " = (fabs(f" << K << ") < 1.7e38) ? (i128)f" << K << " : (i128)0;\n";
+    // the precision check is made on the converted integer: the double nearest to 10^p may lie below 10^p (p = 23, 24, 38) and
+    // is then a legal value. Every |f| < 1.7e38 converts (2^127 > 1.7e38 > 10^38); NaN and the rest are flagged
+    o << "    const bool i" << K << " = fabs(f" << K << ") < 1.7e38;\n";
+    o << "    const i128 " << v << " = i" << K << " ? (i128)f" << K << " : (i128)0;\n";
+    const std::string lim = i128_const(pow10_i128(to.precision));
+    flag("!i" + K + " || " + v + " >= " + lim + " || " + v + " <= -" + lim);
   } else {
     fail(QHIP_UNSUPPORTED, "device cast " + dtype_name(from) + " -> " + dtype_name(to));
   }

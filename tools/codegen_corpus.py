@@ -168,6 +168,21 @@ def entries():
             ex = [b(col(0), op, col(1)) for op in (Op.Add, Op.Sub, Op.Mul, Op.Div, Op.Mod)]
             add(f"arithmetic {tname(t)}" + (", nullable" if nulls else ""), lambda s=s, ex=ex, hn=hn: P.projection_source(s, ex, hn))
     add("arithmetic: checked div/rem in a raw-mode kernel", lambda: P.filter_source(schema(i64, i64), b(b(col(0), Op.Div, col(1)), Op.Gt, b(col(0), Op.Mod, col(1))), [True, False]))
+    # a fused filter gates the flags of keys and arguments (the predicate's own stay unconditional; what has no fallible node is unchanged)
+    fal = schema(i64, i64, f64)
+    quot, narrow8 = b(col(0), Op.Div, col(1)), E.CastExpr(col(2), pa.int32())
+    for nulls in (False, True):
+        hn = [nulls] * len(fal)
+        tag = ", nullable" if nulls else ""
+        add("fallible argument under a predicate" + tag, lambda hn=hn: P.aggregate_source(fal, b(col(1), Op.NotEq, lit(SV.Int64(0))), [narrow8], [E.SumAggregateExpr(quot, i64)], hn))
+        add("fallible argument under a fallible predicate" + tag,
+            lambda hn=hn: P.aggregate_source(fal, b(b(col(0), Op.Mod, col(1)), Op.Eq, lit(SV.Int64(0))), [], [E.SumAggregateExpr(quot, i64)], hn))
+        add("fallible argument, no predicate" + tag, lambda hn=hn: P.aggregate_source(fal, None, [narrow8], [E.SumAggregateExpr(quot, i64)], hn))
+        add("fallible join key under a scan filter: probe" + tag, lambda hn=hn: P.probe_source(fal, [quot, narrow8], gt0, hn))
+        add("fallible join key under a scan filter: build entries" + tag, lambda hn=hn: P.scatter_source(fal, [quot, narrow8], gt0, hn))
+        add("fallible join key under a scan filter: dense build" + tag, lambda hn=hn: P.scatter_source(fal, [quot], gt0, hn), QHIP_PLAN_DENSE=1)
+        add("fallible join key under a scan filter: partition" + tag, lambda hn=hn: P.partition_source(fal, [quot], gt0, 8, hn))
+        add("fallible join key, no scan filter: probe" + tag, lambda hn=hn: P.probe_source(fal, [quot, narrow8], None, hn))
     add("arithmetic: Date32 + Date32 is refused", lambda: P.projection_source(schema(d32, d32), [b(col(0), Op.Add, col(1))]))
     add("arithmetic: mixed integer types are refused", lambda: P.projection_source(schema(i64, i32), [b(col(0), Op.Add, col(1))]))
     add("arithmetic: unknown operator", lambda: P.projection_source(schema(i64, i64), [_binary_raw(col(0), 13, col(1))]))
