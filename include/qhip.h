@@ -324,6 +324,42 @@ int qhip_ctx_csv_pass_ms(const qhip_ctx* ctx, double* out, int32_t n_out);
  * Boolean / Timestamp columns, decoded by kernels of their own — level 1 launches what it always launched. The environment's
  * QHIP_CSV_GRAMMAR (1 / 2) is read when the context is created. */
 int qhip_ctx_set_csv_grammar(qhip_ctx* ctx, int32_t level);
+/* Decode a file of newline-delimited JSON ON THE DEVICE into a table (csrc/json.cpp; replaces
+ * datasource/file/json.rs + the upload). bytes: the file's contents in host memory, read only during the call. schema: a struct
+ * ArrowSchema naming EVERY key a record may hold, with its type. columns / n_columns: the fields to decode, in output order
+ * (NULL / 0 = all, no field twice). batch_rows: a batch boundary every batch_rows rows (<= 0: one batch).
+ * The call is eager and exact or not at all: QHIP_OK with a table whose columns are what qhip_table_from_arrow would hold after
+ * a host parse of the same bytes (Arrow C++'s JSON reader with this schema as explicit_schema), or QHIP_UNSUPPORTED with nothing
+ * created — the message names the first reason and the 1-based record — and the caller takes the host path.
+ * EVERY value of EVERY record is validated by its field's type, projected or not (the host converts every column and refuses
+ * the file on a bad one): a projection saves the stores, the string copies and the output memory, not the walk.
+ * Decoded on the device:
+ *   structure  records end in "\n" or "\r\n", a last record without a line end counts; one object per line, blanks and tabs
+ *              between tokens and around the object; keys are plain strings without a backslash, compared bytewise with the
+ *              schema's names, in any order; a key missing from a record, and the literal null, are NULL for any type
+ *   Int8..Int64, UInt8..UInt64   a number -?(0|[1-9][0-9]*) inside the type's range ("-0" is 0 in a signed column)
+ *   Date32                       an integer number in Int32's range: the days
+ *   Float64                      a JSON number whose digits form an integer <= 2^53 with an effective |power of ten| <= 22
+ *   Decimal128(p, s >= 0)        a JSON number without exponent, at most s fraction digits, |value| < 10^p; or a string without
+ *                                escapes holding -?[0-9]*(.[0-9]*)? with at least one digit under the same limits
+ *   Boolean                      true / false
+ *   Timestamp(s|ms|us|ns), no zone   a string without escapes: YYYY-MM-DD, ' ' or 'T', hh:mm:ss, then '.' and at most as many
+ *                                digits as the unit holds
+ *   Utf8                         a string of valid UTF-8; \" \\ \/ \b \f \n \r \t are replaced by the byte each stands for
+ * Needs the host (QHIP_UNSUPPORTED): a '\r' without '\n', a byte order mark, an empty file, an empty or blank line, 2^32 - 1
+ * records or more; two objects on a line, anything but blanks behind '}', a top-level array, a cut record, a trailing comma; a
+ * key with an escape, an unknown key, a key twice in a record; a value that begins with '{' or '['; a value of another JSON
+ * kind than its column's type; a \uXXXX escape (the next grammar level) or any other byte behind a backslash, a raw byte below
+ * 0x20 in a string, invalid UTF-8, one string of 2 GiB or more, a Utf8 column over 2^31 - 1 bytes; every number, decimal or
+ * timestamp spelling outside the rows above (a fraction or exponent under an integer, leading zeros, 17-digit floats, the
+ * date-only timestamp, 'Z' or an offset); and, before anything is uploaded, a schema with a field of any other type (projected
+ * or not), with a field that is not nullable (the host refuses a record in which such a field is absent or null), with more than
+ * 64 fields, with two fields of one name, or with key names over 1984 bytes in total. */
+int qhip_table_from_json(qhip_ctx* ctx, const struct ArrowSchema* schema, const void* bytes, int64_t n_bytes,
+                         const int32_t* columns, int32_t n_columns, int64_t batch_rows, qhip_table** out);
+/* Device time (ms) of the last qhip_table_from_json's five passes — upload, scan, record starts, decode, Utf8 — when the
+ * context's timing is on (qhip_ctx_set_timing); zeros otherwise. n_out must be 5. */
+int qhip_ctx_json_pass_ms(const qhip_ctx* ctx, double* out, int32_t n_out);
 /* Decode a Parquet file ON THE DEVICE into a table (csrc/parquet.cpp; replaces datasource/file/parquet.rs + the
  * upload). bytes: the whole file in host memory (a read-only mapping will do), read only during the call. schema: a struct
  * ArrowSchema with the Arrow type of EVERY field of the file, in file order (what Arrow's own reader reports for it). columns /

@@ -150,6 +150,8 @@ def load_library() -> C.CDLL:
             "qhip_table_from_arrow_lazy": (C.c_int, [vp, vp, P(vp), i64, P(vp)]),
             "qhip_table_from_csv": (C.c_int, [vp, vp, vp, i64, P(qhip_csv_options), P(i32), i32, i64, P(vp)]),
             "qhip_ctx_csv_pass_ms": (C.c_int, [vp, P(C.c_double), i32]),
+            "qhip_table_from_json": (C.c_int, [vp, vp, vp, i64, P(i32), i32, i64, P(vp)]),
+            "qhip_ctx_json_pass_ms": (C.c_int, [vp, P(C.c_double), i32]),
             "qhip_table_from_parquet": (C.c_int, [vp, vp, vp, i64, P(i32), i32, i64, P(vp)]),
             "qhip_ctx_parquet_pass_ms": (C.c_int, [vp, P(C.c_double), i32]),
             "qhip_ctx_parquet_unpack_ms": (C.c_int, [vp, P(C.c_double)]),
@@ -278,6 +280,12 @@ class Context:
         """Device time (ms) of the last device CSV decode's passes: upload, scan, record starts, decode, Utf8 (timing on)."""
         out = (C.c_double * 5)()
         self.check(self.lib.qhip_ctx_csv_pass_ms(self.handle, out, 5))
+        return list(out)
+
+    def json_pass_ms(self) -> List[float]:
+        """Device time (ms) of the last device JSON decode's passes: upload, scan, record starts, decode, Utf8 (timing on)."""
+        out = (C.c_double * 5)()
+        self.check(self.lib.qhip_ctx_json_pass_ms(self.handle, out, 5))
         return list(out)
 
     def parquet_pass_ms(self) -> List[float]:
@@ -428,6 +436,25 @@ class DeviceTable:
             out = C.c_void_p()
             ctx.check(ctx.lib.qhip_table_from_csv(ctx.handle, C.addressof(c_schema), addr, n, C.byref(opt), cols if columns else None,
                                                   len(columns or []), int(batch_rows or 0), C.byref(out)))
+            return DeviceTable(ctx, out)
+        finally:
+            _release_schema(c_schema)
+
+    @staticmethod
+    def from_json_bytes(ctx: Context, schema: pa.Schema, data, columns: Optional[Sequence[int]] = None, batch_rows: Optional[int] = None) -> "DeviceTable":
+        """Decode the bytes of a newline-delimited JSON file on the device (qhip_table_from_json). `schema` names every key a
+        record may hold; `columns` are the field indices to decode, in output order (None = all). `data`: bytes, or anything with
+        the buffer protocol (an mmap). Raises UnsupportedError, naming the reason and the record, when the file lies outside the
+        device's grammar — the caller then parses on the host."""
+        buf = pa.py_buffer(data)   # (zero copy, read-only buffers too; alive until the call returns)
+        n, addr = buf.size, (C.c_void_p(buf.address) if buf.size else None)
+        cols = (C.c_int32 * max(1, len(columns or [])))(*[int(c) for c in (columns or [])])
+        c_schema = ArrowSchemaStruct()
+        schema._export_to_c(C.addressof(c_schema))
+        try:
+            out = C.c_void_p()
+            ctx.check(ctx.lib.qhip_table_from_json(ctx.handle, C.addressof(c_schema), addr, n, cols if columns else None, len(columns or []),
+                                                   int(batch_rows or 0), C.byref(out)))
             return DeviceTable(ctx, out)
         finally:
             _release_schema(c_schema)

@@ -283,6 +283,8 @@ struct Ctx {
   float wide_join_stage_ms = 0;
   // device time of the last qhip_table_from_csv's passes (csv.cpp; timing on): upload, scan, record starts, decode, Utf8
   float csv_pass_ms[5] = {0, 0, 0, 0, 0};
+  // ... and of the last qhip_table_from_json's (json.cpp): upload, scan, record starts, decode, Utf8
+  float json_pass_ms[5] = {0, 0, 0, 0, 0};
   // ... and of the last qhip_table_from_parquet's (parquet.cpp): upload, levels, string walk, values, Utf8
   float parquet_pass_ms[5] = {0, 0, 0, 0, 0};
   // ... and of its unpack pass (k_pq_unsnap, between "upload" and "levels"): 0 for a file without Snappy pages

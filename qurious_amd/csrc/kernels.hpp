@@ -163,4 +163,18 @@ void launch_csv_copy_utf8(const uint8_t* buf, const uint64_t* strpos, const uint
 void launch_csv_decode_q(const uint8_t* buf, uint64_t n, const uint64_t* starts, uint64_t nrec, const CsvCols& cols, int ncols, uint32_t nfields, int delim,
                          int quote, uint64_t* err, uint64_t* null_counts, uint64_t* utf8_bytes, hipStream_t s);
 void launch_csv_copy_utf8_q(const uint8_t* buf, const uint64_t* strpos, const uint32_t* offsets, uint64_t nrows, uint8_t* data, int quote, hipStream_t s);
+
+// ---- newline-delimited JSON -> typed columns (kernels_json.hip, device/qhip_json.inc; json.cpp qhip_table_from_json). The record
+// ends and starts come from launch_csv_scan (quote = -1) and launch_csv_starts as they are.
+struct JsonOut { void* values; uint64_t* valid; uint64_t* strpos; };                                              // = qh_json_out
+struct JsonField { uint16_t name_off, name_len; uint8_t kind; int8_t col; uint8_t a, b; };                       // = qh_json_field
+constexpr int kJsonFields = 64;
+constexpr int kJsonNameBytes = 1984;
+struct JsonDesc { JsonOut out[kJsonFields]; JsonField field[kJsonFields]; uint8_t names[kJsonNameBytes]; };      // = qh_json_desc
+// one record per lane. status: [0] the first offender (record << 8 | reason, atomicMin), [2 + c] NULL count and [2 + 64 + c] Utf8
+// byte total of output column c
+void launch_json_decode(const uint8_t* buf, uint64_t n, const uint64_t* starts, uint64_t nrec, const JsonDesc& desc, uint32_t nfields, uint64_t* status,
+                        hipStream_t s);
+// the copy that removes the backslash escapes of the rows whose strpos carries QH_JSON_POS_ESC; other rows as launch_csv_copy_utf8
+void launch_json_copy_utf8(const uint8_t* buf, const uint64_t* strpos, const uint32_t* offsets, uint64_t nrows, uint8_t* data, hipStream_t s);
 }  // namespace qhip

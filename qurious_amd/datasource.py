@@ -11,6 +11,8 @@ CSV files can instead be decoded ON THE DEVICE (`read_csv(device=True)` / QHIP_C
 text crosses PCIe once and unread columns are never parsed; a file outside the device's strict grammar takes the host path.
 So can Parquet files (`read_parquet(device=True)` / QHIP_PARQUET_DEVICE=1, off by default): only the projected
 column chunks cross PCIe; format level 1 (uncompressed, data pages V1, flat columns), everything else takes the host path.
+And newline-delimited JSON (`read_json(device=True)` / QHIP_JSON_DEVICE=1, off by default): flat objects of
+scalar values; nested values, \\uXXXX escapes and every lenient spelling take the host path.
 
 Divergence note: with `schema=None` the column types come from Arrow C++'s CSV / JSON type inference, which is close to
 but not the same code as arrow-rs' `Format::infer_schema` (csv.rs:58); pass an explicit schema for exact control."""
@@ -40,7 +42,7 @@ def _table_of(tbl: pa.Table, batch_rows: Optional[int]) -> MemoryTable:
 
 
 class DeviceDecodedTable(MemoryTable):
-    """A file decoded on the device (qhip_table_from_csv, qhip_table_from_parquet): `device_table()` IS the decoded table, nothing
+    """A file decoded on the device (qhip_table_from_csv, qhip_table_from_parquet, qhip_table_from_json): `device_table()` IS the decoded table, nothing
     was parsed on the host. `.data` — what the oracle, `insert` and `delete` work on — is downloaded the first time somebody asks for it;
     from then on MemoryTable's rule holds (the device copy is kept for as long as `data` holds the very batches it stands for)."""
 
@@ -190,7 +192,64 @@ def read_parquet(path: str, columns: Optional[Sequence[str]] = None, batch_rows:
     return t
 
 
-def read_json(path: str, batch_rows: Optional[int] = 1 << 20) -> MemoryTable:
-    """read_json (datasource/file/json.rs): newline-delimited JSON"""
+def _host_read_json(path, schema, batch_rows, columns) -> MemoryTable:
     import pyarrow.json as pajson
-    return _table_of(pajson.read_json(path), batch_rows)
+    tbl = pajson.read_json(path, parse_options=pajson.ParseOptions(explicit_schema=schema)) if schema is not None else pajson.read_json(path)
+    if columns is not None:
+        tbl = tbl.select(list(columns))
+    return _table_of(tbl, batch_rows)
+
+
+def _device_read_json(path, schema, batch_rows, columns) -> Optional[MemoryTable]:
+    """the device path, or None when the file needs the host path (QHIP_UNSUPPORTED, or a file Arrow itself cannot open)"""
+    import mmap
+    import os
+    import pyarrow.json as pajson
+    from ._ffi import UnsupportedError, get_context
+    try:
+        if os.path.getsize(path) == 0:
+            return None
+        if schema is None:
+            # the types the host path infers from the first block it reads; a later block that would change one of them, or add
+            # a key, fails the strict decode and the file takes the host read
+            with pajson.open_json(path) as rd:
+                schema = rd.schema
+    except (pa.ArrowException, OSError):
+        return None
+    if len(set(schema.names)) != len(schema.names) or not all(f.nullable for f in schema):
+        return None   # (the host refuses a record in which a required field is absent or null: such a schema stays with it)
+    schema = pa.schema([pa.field(f.name, f.type) for f in schema])   # as the host parse returns it: no metadata
+    idx = None
+    if columns is not None:
+        idx = [schema.get_field_index(c) for c in columns]
+        if any(k < 0 for k in idx) or len(set(idx)) != len(idx):
+            return None
+    with open(path, "rb") as f, mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ) as m:
+        try:
+            dev = DeviceTable.from_json_bytes(get_context(), schema, m, columns=idx, batch_rows=batch_rows)
+        except UnsupportedError:
+            return None
+    out_schema = schema if idx is None else pa.schema([schema.field(k) for k in idx])
+    return DeviceDecodedTable(out_schema, dev)
+
+
+def read_json(path: str, batch_rows: Optional[int] = 1 << 20, schema: Optional[pa.Schema] = None, columns: Optional[Sequence[str]] = None,
+              device: Optional[bool] = None) -> MemoryTable:
+    """read_json (datasource/file/json.rs): newline-delimited JSON, one object per line. `schema`: the keys and their types
+    (Arrow's `explicit_schema`; None: Arrow infers them); `columns`: the names of the columns to keep, in output order.
+
+    device=True (None: the environment's QHIP_JSON_DEVICE, default 0): the file's text is decoded on the device
+    (qhip_table_from_json) and the result's `decoded_on_device` is True. With `schema=None` the device takes the
+    types Arrow infers from the file's first block. A file outside the device's strict grammar — nested values, \\uXXXX escapes,
+    unknown or repeated keys, lenient number spellings, ... — falls back silently to the host read below, which also produces
+    every error message."""
+    import os
+    if device is None:
+        device = os.environ.get("QHIP_JSON_DEVICE", "0") not in ("", "0")
+    if device:
+        t = _device_read_json(path, schema, batch_rows, columns)
+        if t is not None:
+            return t
+    t = _host_read_json(path, schema, batch_rows, columns)
+    t.decoded_on_device = False
+    return t

@@ -226,6 +226,17 @@ extern "C" {
         out: *mut *mut qhip_table,
     ) -> c_int;
     pub fn qhip_ctx_csv_pass_ms(ctx: *const qhip_ctx, out: *mut f64, n_out: i32) -> c_int;
+    pub fn qhip_table_from_json(
+        ctx: *mut qhip_ctx,
+        schema: *const FFI_ArrowSchema,
+        bytes: *const c_void,
+        n_bytes: i64,
+        columns: *const i32,
+        n_columns: i32,
+        batch_rows: i64,
+        out: *mut *mut qhip_table,
+    ) -> c_int;
+    pub fn qhip_ctx_json_pass_ms(ctx: *const qhip_ctx, out: *mut f64, n_out: i32) -> c_int;
     pub fn qhip_table_from_parquet(
         ctx: *mut qhip_ctx,
         schema: *const FFI_ArrowSchema,

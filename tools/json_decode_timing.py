@@ -1,0 +1,171 @@
+"""What getting a newline-delimited JSON table onto the device costs: about --gb GB of lineitem-shaped records
+(synth.lineitem, one object per line, written once into a temporary directory), and per measurement the median of --runs calls
+after --warmup calls, each ending in a device synchronise:
+
+  (a) host path    datasource.read_json(device=False) — Arrow C++ parse with --threads threads — plus the eager upload of every
+                   column
+  (b) device path  datasource.read_json(device=True) as a whole call: mmap, upload of the text, the kernels, both host waits
+  (c) floor        one plain host-to-device copy of the file's bytes out of the same mapping (hipMemcpy, pageable source)
+  (d) passes       HIP events around the device path's passes (timing on, calls of their own): upload, k_csv_scan, record starts
+                   (scan of the chunk counts + k_csv_scan<true>), k_json_decode, Utf8 (offset scans + k_json_copy_utf8), with the
+                   GB/s of file bytes each pass amounts to
+
+(a) .. (c) alternate in one process, --repeat times.
+
+--comment: the same records with a comment column l_comment of 16 to 80 bytes, of which one value in 32 holds a word in escaped
+quotes (\\") and one in 16 an escaped line feed (\\n): the rows the unescaping copy is for.
+
+    python tools/json_decode_timing.py [--gb 1.0] [--runs 10] [--warmup 2] [--repeat 2] [--threads 16] [--comment]
+"""
+import argparse
+import ctypes as C
+import mmap
+import os
+import statistics
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+import pyarrow as pa  # noqa: E402
+import pyarrow.compute as pc  # noqa: E402
+
+import qurious_amd as q  # noqa: E402
+from qurious_amd import datasource, synth  # noqa: E402
+from qurious_amd._ffi import DeviceTable  # noqa: E402
+
+PASSES = ["upload", "k_csv_scan", "record starts", "k_json_decode", "Utf8 offsets + k_json_copy_utf8"]
+
+COMMENT_WORDS = ["carefully", "final deposits", "blithely ironic", "requests, packages", "slyly even", "accounts sleep, furiously", "pending", "quickly"]
+
+
+def comment_column(first_row, n):
+    """TPC-H-like comments out of a pool of 4096, as JSON string bodies: one in 32 holds a word in escaped quotes, one in 16 an
+    escaped line feed"""
+    pool = []
+    for k in range(4096):
+        first = COMMENT_WORDS[k % 8]
+        if k % 32 == 5:
+            first = '\\"' + first + '\\"'
+        sep = "\\n" if k % 16 == 9 else ", "
+        pool.append(first + sep + COMMENT_WORDS[(k // 8) % 8] + (" " + COMMENT_WORDS[(k // 64) % 8] if k % 3 else ""))
+    idx = (np.arange(first_row, first_row + n, dtype=np.int64) * 2654435761 >> 7) % len(pool)
+    return pa.array(pool, pa.string()).take(pa.array(idx))
+
+
+def json_lines(tbl, comment):
+    """one string per row: the record and its line feed (Date32 as its number of days, Decimal128 as a JSON number, strings in quotes)"""
+    parts = []
+    for k, f in enumerate(tbl.schema):
+        col = tbl.column(k).combine_chunks()
+        parts.append(("{" if k == 0 else ",") + '"%s":' % f.name + ('"' if pa.types.is_string(f.type) else ""))
+        if pa.types.is_date32(f.type):
+            col = col.cast(pa.int32())
+        parts.append(col.cast(pa.string()))
+        if pa.types.is_string(f.type):
+            parts.append('"')
+    if comment is not None:
+        parts += [',"l_comment":"', comment, '"']
+    parts += ["}\n", ""]
+    return pc.binary_join_element_wise(*parts)
+
+
+def write_file(path, target_bytes, comment=False):
+    """lineitem rows until the file has about target_bytes; returns the row count"""
+    step, rows = 1 << 20, 0
+    with open(path, "wb") as f:
+        while f.tell() < target_bytes:
+            tbl = pa.Table.from_batches([synth.lineitem_batch(rows, step)])
+            lines = json_lines(tbl, comment_column(rows, step) if comment else None)
+            off = lines.buffers()[1]
+            first, last = np.frombuffer(off, dtype=np.int32, count=len(lines) + 1, offset=lines.offset * 4)[[0, -1]]
+            f.write(memoryview(lines.buffers()[2])[int(first):int(last)])   # (the values buffer IS the rows one after the other)
+            rows += step
+    return rows
+
+
+def median_ms(fn, runs, warmup):
+    for _ in range(warmup):
+        fn()
+    out = []
+    for _ in range(runs):
+        t0 = time.perf_counter()
+        fn()
+        out.append((time.perf_counter() - t0) * 1e3)
+    return statistics.median(out), min(out)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--gb", type=float, default=1.0)
+    ap.add_argument("--runs", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--repeat", type=int, default=2)
+    ap.add_argument("--threads", type=int, default=16)
+    ap.add_argument("--comment", action="store_true", help="a comment column whose values hold escaped quotes and line feeds")
+    args = ap.parse_args()
+    pa.set_cpu_count(args.threads)
+    ctx = q.get_context()
+    schema = pa.schema([pa.field(f.name, f.type) for f in synth.LINEITEM_SCHEMA])
+    if args.comment:
+        schema = schema.append(pa.field("l_comment", pa.string()))
+    hip = C.CDLL(None)   # (libqhip.so is loaded globally and brings the HIP runtime with it)
+    hip.hipMalloc.argtypes, hip.hipMemcpy.argtypes, hip.hipFree.argtypes = [C.POINTER(C.c_void_p), C.c_size_t], [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int], [C.c_void_p]
+    with tempfile.TemporaryDirectory() as d:
+        path = os.path.join(d, "lineitem.json")
+        rows = write_file(path, int(args.gb * 1e9), args.comment)
+        nbytes = os.path.getsize(path)
+        kind = ", with l_comment (escapes)" if args.comment else ""
+        print(f"device {ctx.device_name()}; {path}: {nbytes} bytes, {rows} rows, {nbytes / rows:.1f} bytes per record{kind}; median (min) of {args.runs} calls "
+              f"after {args.warmup} warm-up calls; host parse with {args.threads} threads", flush=True)
+
+        def host_path():
+            t = datasource.read_json(path, schema=schema, device=False)
+            dev = DeviceTable.from_batches(ctx, t.schema(), t.data, lazy=False)
+            ctx.synchronize()
+            return dev
+
+        def device_path():
+            t = datasource.read_json(path, schema=schema, device=True)
+            assert t.decoded_on_device
+            ctx.synchronize()
+            return t.device_table()
+
+        dst = C.c_void_p()
+        assert hip.hipMalloc(C.byref(dst), nbytes + 64) == 0
+        f = open(path, "rb")
+        m = mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ)
+        src = pa.py_buffer(m)
+
+        def floor():
+            assert hip.hipMemcpy(dst, C.c_void_p(src.address), nbytes, 1) == 0   # (hipMemcpyHostToDevice; returns when the copy is done)
+
+        assert host_path().num_rows == device_path().num_rows == rows
+        for rep in range(args.repeat):
+            for name, fn in (("(a) host parse + upload", host_path), ("(b) device path, whole call", device_path), ("(c) plain copy of the file", floor)):
+                med, low = median_ms(fn, args.runs, args.warmup)
+                print(f"run {rep + 1} {name:30s} {med:9.2f} ms (min {low:9.2f})  {nbytes / med / 1e6:8.2f} GB/s of file bytes", flush=True)
+        ctx.set_timing(True)
+        per = []
+        for _ in range(args.warmup + args.runs):
+            device_path()
+            per.append(ctx.json_pass_ms())
+        ctx.set_timing(False)
+        per = per[args.warmup:]
+        kernels = 0.0
+        for k, name in enumerate(PASSES):
+            med = statistics.median(p[k] for p in per)
+            kernels += med if k else 0.0
+            print(f"(d) {name:32s} {med:9.3f} ms  {nbytes / max(med, 1e-6) / 1e6:9.1f} GB/s of file bytes", flush=True)
+        print(f"(d) kernels together (all but the upload) {kernels:9.3f} ms  {nbytes / max(kernels, 1e-6) / 1e6:9.1f} GB/s of file bytes", flush=True)
+        del src
+        m.close()
+        f.close()
+        hip.hipFree(dst)
+
+
+if __name__ == "__main__":
+    main()
