@@ -379,9 +379,9 @@ int qhip_ctx_json_pass_ms(const qhip_ctx* ctx, double* out, int32_t n_out);
  * writes by default: their pages cross PCIe compressed and are unpacked on the device; a page whose stream is damaged, or which
  * claims more than 64/3 times its compressed size, needs the host ("Snappy").
  * Needs the host: a compressed projected chunk (level 1: every codec, so write with compression="NONE" or set level 2; level 2:
- * every codec but SNAPPY — zstd, gzip, lz4, brotli), data pages V2, index
+ * every codec but SNAPPY — zstd, gzip, lz4, brotli), data pages V2 (encoding set 1; qhip_ctx_set_parquet_encodings below), index
  * pages, an encrypted footer, a group / list / map field anywhere in the schema, a chunk with file_path, any other encoding
- * (DELTA_*, BYTE_STREAM_SPLIT, RLE values), BIT_PACKED levels, every other type pair (a zoned Timestamp, Date64, Time, Float16,
+ * (DELTA_*, BYTE_STREAM_SPLIT, RLE values; encoding set 2 decodes these but DELTA_BYTE_ARRAY), BIT_PACKED levels, every other type pair (a zoned Timestamp, Date64, Time, Float16,
  * Decimal256, INT96, LargeUtf8, Binary, dictionary-typed fields), a stored value outside an Int8/Int16/UInt8/UInt16 column's
  * range, a Utf8 column over 2^31 - 1 bytes, more than 64 projected columns, 0 rows, 2^32 - 1 rows or more, and every offset,
  * length, count or index that points outside the file, its chunk, its page or its dictionary ("corrupt"): no host or device
@@ -400,6 +400,35 @@ int qhip_ctx_parquet_unpack_ms(const qhip_ctx* ctx, double* out);
  * QHIP_INVALID_ARGUMENT and leaves the level as it was. The environment's QHIP_PARQUET_FORMAT (1 / 2) is read when the context
  * is created. */
 int qhip_ctx_set_parquet_format(qhip_ctx* ctx, int32_t level);
+/* The page kinds and value encodings qhip_table_from_parquet decodes, independent of the format level (which says which codecs):
+ * a Snappy file with data pages V2 needs level 2 and set 2. set 1 (the default): data pages V1 with PLAIN or dictionary values,
+ * as described above. set 2 adds, for flat columns: data pages V2 (num_rows = num_values, no repetition levels, the values part
+ * alone compressed, or left uncompressed where the page says so; the device counts the NULLs and refuses a num_nulls that differs); RLE Boolean values, which V2 writers use
+ * for every Boolean column; BYTE_STREAM_SPLIT for FLOAT, DOUBLE, INT32, INT64 and FIXED_LEN_BYTE_ARRAY decimals;
+ * DELTA_BINARY_PACKED for INT32 and INT64 under every annotation listed above (block size a positive multiple of 128 up to
+ * 65536, miniblocks dividing it into multiples of 32 values, wrapping arithmetic in the type's width); DELTA_LENGTH_BYTE_ARRAY
+ * for Utf8. Delta pages are decoded by a pass of their own (k_pq_delta) and the new value encodings by a second instance of the
+ * values kernel; a file with none of them launches what set 1 launches.
+ * Still needs the host at set 2: DELTA_BYTE_ARRAY (every value needs its predecessor's bytes), RLE values of anything but
+ * BOOLEAN, delta blocks above 65536 values, and everything else on the list
+ * above (nested columns, other codecs, INT96, ...).
+ * Any other set answers QHIP_INVALID_ARGUMENT and leaves the set as it was. The environment's QHIP_PARQUET_ENCODINGS (1 / 2) is
+ * read when the context is created. */
+int qhip_ctx_set_parquet_encodings(qhip_ctx* ctx, int32_t set);
+/* Device time (ms) of the delta pass (encoding set 2: DELTA_* pages -> the decoded area) of the last qhip_table_from_parquet, or
+ * of the last qhip_parquet_delta_decode's kernel, when the context's timing is on; 0 otherwise and for a file without such
+ * pages. The pass runs between "levels" and "string walk" and belongs to neither of qhip_ctx_parquet_pass_ms's five values. */
+int qhip_ctx_parquet_delta_ms(const qhip_ctx* ctx, double* out);
+/* A testing and measurement aid: the device DELTA_BINARY_PACKED decoder of encoding set 2 over raw streams (as a Parquet page
+ * holds them). bytes: the n_streams streams, stream k in bytes[src_offsets[k] .. src_offsets[k + 1]); widths[k]: 4 (INT32) or 8
+ * (INT64); counts[k]: the number of values the caller expects (a page's non-NULL rows; at most 2^28 - 1). The streams are
+ * uploaded and decoded one wavefront each; the values of stream k, counts[k] x widths[k] bytes little-endian, lie one stream
+ * behind the other in out (out_bytes >= the sum). end_pos[k]: the byte position within stream k where it ended (behind the
+ * last miniblock that holds a value), -1 for a refused stream. status[k]: 0, or the Parquet needs-host reason
+ * (QH_PQ_R_DELTA_*, csrc/device/qhip_parquet.inc) for which stream k was refused — a refused stream is a normal return, its bytes
+ * in out are unspecified, and the other streams of the call are decoded all the same. */
+int qhip_parquet_delta_decode(qhip_ctx* ctx, const void* bytes, int64_t n_bytes, const int64_t* src_offsets, const int32_t* widths,
+                              const int64_t* counts, int64_t n_streams, void* out, int64_t out_bytes, int64_t* end_pos, int32_t* status);
 /* A testing and measurement aid: the device Snappy decoder of format level 2 over raw Snappy streams (no framing, as a Parquet
  * page holds them). bytes: the n_streams streams, stream k in bytes[src_offsets[k] .. src_offsets[k + 1]); dst_sizes[k]: the
  * uncompressed size the caller declares for it (a page header's uncompressed_page_size). The streams are uploaded, unpacked one

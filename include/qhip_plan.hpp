@@ -47,6 +47,9 @@ class Context {
   void set_csv_grammar(int level) const { check(qhip_ctx_set_csv_grammar(ctx_, level)); }
   // the device Parquet decoder's format level (qhip.h: 1 uncompressed chunks only, 2 also Snappy chunks)
   void set_parquet_format(int level) const { check(qhip_ctx_set_parquet_format(ctx_, level)); }
+  // the device Parquet decoder's encoding set (qhip.h: 1 pages V1 with PLAIN or dictionary values, 2 also pages V2, RLE Booleans,
+  // BYTE_STREAM_SPLIT, DELTA_BINARY_PACKED and DELTA_LENGTH_BYTE_ARRAY)
+  void set_parquet_encodings(int set) const { check(qhip_ctx_set_parquet_encodings(ctx_, set)); }
 
  private:
   qhip_ctx* ctx_ = nullptr;

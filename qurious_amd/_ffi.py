@@ -157,6 +157,9 @@ def load_library() -> C.CDLL:
             "qhip_ctx_parquet_unpack_ms": (C.c_int, [vp, P(C.c_double)]),
             "qhip_ctx_set_parquet_format": (C.c_int, [vp, i32]),
             "qhip_snappy_decode": (C.c_int, [vp, vp, i64, P(i64), P(i64), i64, vp, i64, P(i32)]),
+            "qhip_ctx_set_parquet_encodings": (C.c_int, [vp, i32]),
+            "qhip_ctx_parquet_delta_ms": (C.c_int, [vp, P(C.c_double)]),
+            "qhip_parquet_delta_decode": (C.c_int, [vp, vp, i64, P(i64), P(i32), P(i64), i64, vp, i64, P(i64), P(i32)]),
             "qhip_table_to_arrow": (C.c_int, [vp, vp, i64, vp, vp]),
             "qhip_table_num_batches": (i64, [vp]),
             "qhip_table_batch_offsets": (C.c_int, [vp, P(i64), i64]),
@@ -305,6 +308,48 @@ class Context:
         """The device Parquet decoder's format level: 1 (the default) uncompressed chunks only, a compressed file needs the host;
         2 also SNAPPY chunks — pyarrow's default — unpacked on the device. QHIP_PARQUET_FORMAT sets it when the context is made."""
         self.check(self.lib.qhip_ctx_set_parquet_format(self.handle, int(level)))
+
+    def set_parquet_encodings(self, encodings: int):
+        """The device Parquet decoder's encoding set, independent of the format level: 1 (the default) data pages V1 with PLAIN
+        or dictionary values; 2 also data pages V2, RLE Boolean values, BYTE_STREAM_SPLIT, DELTA_BINARY_PACKED and
+        DELTA_LENGTH_BYTE_ARRAY. QHIP_PARQUET_ENCODINGS sets it when the context is made."""
+        self.check(self.lib.qhip_ctx_set_parquet_encodings(self.handle, int(encodings)))
+
+    def parquet_delta_ms(self) -> float:
+        """Device time (ms) of the delta pass (k_pq_delta, encoding set 2) of the last device Parquet decode, or of the last
+        `delta_decode`'s kernel (timing on). It lies between "levels" and "string walk" and is part of neither."""
+        out = C.c_double(0)
+        self.check(self.lib.qhip_ctx_parquet_delta_ms(self.handle, C.byref(out)))
+        return float(out.value)
+
+    def delta_decode(self, streams: Sequence[bytes], widths: Sequence[int], counts: Sequence[int]):
+        """A testing and measurement aid (qhip_parquet_delta_decode): raw DELTA_BINARY_PACKED streams through the device decoder
+        of encoding set 2, one wavefront each, in one call. `widths[k]`: 4 or 8; `counts[k]`: the values expected of stream k.
+        Returns (values, ends, statuses): statuses[k] is 0 or the needs-host reason (QH_PQ_R_DELTA_*) for which stream k was
+        refused, values[k] its values as unsigned integers of its width (None when refused), ends[k] the byte position where
+        the stream ended."""
+        n = len(streams)
+        data = b"".join(streams)
+        off = (C.c_int64 * (n + 1))()
+        for k, s in enumerate(streams):
+            off[k + 1] = off[k] + len(s)
+        wd = (C.c_int32 * max(n, 1))(*[int(v) for v in widths])
+        cnt = (C.c_int64 * max(n, 1))(*[int(v) for v in counts])
+        total = sum(int(c) * int(w) for c, w in zip(counts, widths))
+        out = C.create_string_buffer(max(total, 1))
+        ends = (C.c_int64 * max(n, 1))()
+        status = (C.c_int32 * max(n, 1))()
+        self.check(self.lib.qhip_parquet_delta_decode(self.handle, data, len(data), off, wd, cnt, n, out, total, ends, status))
+        values, at, raw = [], 0, out.raw
+        for k in range(n):
+            nb = int(counts[k]) * int(widths[k])
+            if status[k] == 0:
+                w = int(widths[k])
+                values.append([int.from_bytes(raw[at + i:at + i + w], "little") for i in range(0, nb, w)])
+            else:
+                values.append(None)
+            at += nb
+        return values, [int(ends[k]) for k in range(n)], [int(status[k]) for k in range(n)]
 
     def snappy_decode(self, streams: Sequence[bytes], dst_sizes: Sequence[int]):
         """A testing and measurement aid (qhip_snappy_decode): raw Snappy streams through the device decoder of format level 2,

@@ -292,6 +292,12 @@ struct Ctx {
   // the device Parquet decoder's format level (parquet.cpp): 1 = uncompressed chunks only, 2 = + SNAPPY chunks;
   // QHIP_PARQUET_FORMAT at context creation, qhip_ctx_set_parquet_format later
   int parquet_format = 1;
+  // ... and its encoding set, independent of the level: 1 = data pages V1 with PLAIN / dictionary values, 2 = + data pages V2,
+  // RLE Boolean values, BYTE_STREAM_SPLIT, DELTA_BINARY_PACKED, DELTA_LENGTH_BYTE_ARRAY; QHIP_PARQUET_ENCODINGS at context
+  // creation, qhip_ctx_set_parquet_encodings later
+  int parquet_encodings = 1;
+  // device time of the delta pass (k_pq_delta, between "levels" and "string walk"): 0 for a file without DELTA_* pages
+  float parquet_delta_ms = 0;
   // the device CSV decoder's grammar level (csv.cpp): 1 = plain fields only, 2 = + canonical quoted fields, Boolean, Timestamp;
   // QHIP_CSV_GRAMMAR at context creation, qhip_ctx_set_csv_grammar later
   int csv_grammar = 1;

@@ -351,6 +351,7 @@ int qhip_ctx_create(int device_index, qhip_ctx** out) {
     c->timing = env_int("QHIP_TIMING", 0) != 0;
     c->csv_grammar = env_int("QHIP_CSV_GRAMMAR", 1) == 2 ? 2 : 1;
     c->parquet_format = env_int("QHIP_PARQUET_FORMAT", 1) == 2 ? 2 : 1;
+    c->parquet_encodings = env_int("QHIP_PARQUET_ENCODINGS", 1) == 2 ? 2 : 1;
     c->pinned_bytes = 256 * 1024;
     QHIP_HIP_CHECK(hipHostMalloc(&c->pinned, c->pinned_bytes, hipHostMallocDefault));
     memset(&c->stats, 0, sizeof(c->stats));
@@ -424,6 +425,12 @@ int qhip_ctx_set_csv_grammar(qhip_ctx* ctx, int32_t level) {
 int qhip_ctx_set_parquet_format(qhip_ctx* ctx, int32_t level) {
   if (!ctx || level < 1 || level > 2) return QHIP_INVALID_ARGUMENT;
   ctx->parquet_format = level;
+  return QHIP_OK;
+}
+
+int qhip_ctx_set_parquet_encodings(qhip_ctx* ctx, int32_t set) {
+  if (!ctx || set < 1 || set > 2) return QHIP_INVALID_ARGUMENT;
+  ctx->parquet_encodings = set;
   return QHIP_OK;
 }
 

@@ -59,7 +59,22 @@ typedef long long pq_i64;
 #define QH_PQ_R_SNAPPY_INPUT 31    // an element past the end of its stream, or stream and page do not end together
 #define QH_PQ_R_SNAPPY_OUTPUT 32   // an element past uncompressed_page_size
 #define QH_PQ_R_SNAPPY_OFFSET 33   // a copy offset of 0 or beyond the bytes produced
-#define QH_PQ_R_COUNT 34
+// (encoding set 2, qhip_ctx_set_parquet_encodings: data pages V2, RLE Booleans, BYTE_STREAM_SPLIT, DELTA_*; device/qhip_delta.inc)
+#define QH_PQ_R_V2_UNCOMPRESSED 34 // a data page V2 with is_compressed = false whose two sizes differ
+#define QH_PQ_R_V2_LEVELS 35       // a data page V2 whose level lengths point past the page, or definition levels in a required column
+#define QH_PQ_R_V2_REPETITION 36   // a data page V2 with repetition levels
+#define QH_PQ_R_V2_ROWS 37         // a data page V2 whose num_rows is not its num_values
+#define QH_PQ_R_V2_NULLS 38        // a data page V2 whose num_nulls is not what its levels say
+#define QH_PQ_R_RLE_LENGTH 39      // RLE Boolean values whose length prefix points past the page, or a value above 1
+#define QH_PQ_R_BSS_SIZE 40        // a BYTE_STREAM_SPLIT region that is not (non-NULL rows) x (value width) bytes
+#define QH_PQ_R_DELTA_VARINT 41    // a DELTA_BINARY_PACKED varint of more than 64 bits
+#define QH_PQ_R_DELTA_GEOMETRY 42  // block size 0 or no multiple of 128, miniblocks 0 or no divisor, values per miniblock no multiple of 32
+#define QH_PQ_R_DELTA_LARGE 43     // a block of more than 65 536 values
+#define QH_PQ_R_DELTA_COUNT 44     // the stream's total count is not the page's non-NULL rows
+#define QH_PQ_R_DELTA_SHORT 45     // the stream ends inside its header, a block header, the width bytes or a miniblock
+#define QH_PQ_R_DELTA_WIDTH 46     // a miniblock that holds a value has a bit width above the type's
+#define QH_PQ_R_DELTA_LENGTH 47    // DELTA_LENGTH_BYTE_ARRAY: a negative length, or lengths that add up past the page
+#define QH_PQ_R_COUNT 48
 
 QH_PQ_HD inline const char* qh_pq_reason_text(unsigned r) {
   switch (r) {
@@ -96,6 +111,20 @@ QH_PQ_HD inline const char* qh_pq_reason_text(unsigned r) {
     case QH_PQ_R_SNAPPY_INPUT: return "corrupt: a Snappy element past the end of its page, or a page whose stream and size do not end together";
     case QH_PQ_R_SNAPPY_OUTPUT: return "corrupt: a Snappy element past uncompressed_page_size";
     case QH_PQ_R_SNAPPY_OFFSET: return "corrupt: a Snappy copy offset of 0 or beyond the bytes produced";
+    case QH_PQ_R_V2_UNCOMPRESSED: return "corrupt: a data page V2 marked uncompressed whose compressed and uncompressed sizes differ";
+    case QH_PQ_R_V2_LEVELS: return "corrupt: a data page V2 whose level lengths point past the page, or levels in a required column";
+    case QH_PQ_R_V2_REPETITION: return "a data page V2 with repetition levels";
+    case QH_PQ_R_V2_ROWS: return "a data page V2 whose num_rows differs from num_values";
+    case QH_PQ_R_V2_NULLS: return "corrupt: a data page V2 whose num_nulls differs from its levels";
+    case QH_PQ_R_RLE_LENGTH: return "corrupt: RLE Boolean values whose length points past the page, or a value above 1";
+    case QH_PQ_R_BSS_SIZE: return "corrupt: a BYTE_STREAM_SPLIT region that is not non-NULL rows times the value width";
+    case QH_PQ_R_DELTA_VARINT: return "corrupt: a DELTA_BINARY_PACKED varint of more than 64 bits";
+    case QH_PQ_R_DELTA_GEOMETRY: return "corrupt: a DELTA_BINARY_PACKED block size or miniblock count outside the format's rules";
+    case QH_PQ_R_DELTA_LARGE: return "a DELTA_BINARY_PACKED block of more than 65536 values";
+    case QH_PQ_R_DELTA_COUNT: return "corrupt: a DELTA_BINARY_PACKED total count that differs from the page's non-NULL rows";
+    case QH_PQ_R_DELTA_SHORT: return "corrupt: a DELTA_BINARY_PACKED stream that ends inside a header or a miniblock";
+    case QH_PQ_R_DELTA_WIDTH: return "corrupt: a DELTA_BINARY_PACKED bit width above the type's bits";
+    case QH_PQ_R_DELTA_LENGTH: return "corrupt: a DELTA_LENGTH_BYTE_ARRAY length that is negative or points past its page";
     default: return "outside the device's Parquet coverage";
   }
 }
@@ -104,6 +133,13 @@ QH_PQ_HD inline const char* qh_pq_reason_text(unsigned r) {
 #define QH_PQ_ENC_PLAIN 0u
 #define QH_PQ_ENC_DICT 1u       // RLE_DICTIONARY / PLAIN_DICTIONARY indices over the chunk's dictionary page
 #define QH_PQ_ENC_DICTPAGE 2u   // the dictionary page itself: only the string walk looks at it (Utf8)
+// (encoding set 2: k_pq_values leaves these pages to k_pq_values_ext)
+#define QH_PQ_ENC_RLE_BOOL 3u   // BOOLEAN values as the hybrid at width 1 behind a 4-byte length
+#define QH_PQ_ENC_BSS 4u        // BYTE_STREAM_SPLIT: byte j of value idx at j * (non-NULL rows) + idx
+#define QH_PQ_ENC_DELTA 5u      // DELTA_BINARY_PACKED: k_pq_delta leaves the values dense (PLAIN) in the page's slot at dict_pos
+#define QH_PQ_ENC_DELTA_LEN 6u  // DELTA_LENGTH_BYTE_ARRAY: k_pq_delta writes the page's (length, position) entries
+
+#define QH_PQ_F_V2 1u           // a data page V2: its levels lie at lev_pos without a length prefix, its values begin at pos
 
 // physical layout of a stored value
 #define QH_PQ_P_BOOL 0u
@@ -117,7 +153,7 @@ QH_PQ_HD inline const char* qh_pq_reason_text(unsigned r) {
 typedef struct qh_pq_page {
   pq_u64 pos;         // the page's payload (behind its header)
   pq_u64 first_row;   // data page: its first row in the output column
-  pq_u64 dict_pos;    // data page: the chunk's dictionary page payload; dictionary page: unused
+  pq_u64 dict_pos;    // data page: the chunk's dictionary page payload (QH_PQ_ENC_DELTA: its slot in the decoded area); dictionary page: unused
   pq_u64 ent;         // Utf8: where this page's (length, position) entries begin in the column's entry array
   pq_u32 size;        // payload bytes
   pq_u32 num_values;  // data page: rows; dictionary page: entries
@@ -125,7 +161,24 @@ typedef struct qh_pq_page {
   pq_u32 enc;         // QH_PQ_ENC_*
   pq_u32 dict_size;   // data page: the dictionary payload's bytes
   pq_u32 dict_n;      // ... and its entry count (fixed widths: dict_n * width <= dict_size was checked on the host)
+  pq_u64 lev_pos;     // data page V2: its definition levels, lev_size bytes in the uploaded chunks (never compressed)
+  pq_u32 lev_size;
+  pq_u32 flags;       // QH_PQ_F_*
+  pq_u32 num_nulls;   // data page V2: what its header claims; the level pass counts
+  pq_u32 pad;
 } qh_pq_page;
+
+// one DELTA_BINARY_PACKED stream for k_pq_delta (encoding set 2). Of a page: src, src_size and count come from the page and the
+// level pass's state on the device. Of a raw stream (qhip_parquet_delta_decode): they stand here.
+typedef struct qh_pq_dstream {
+  pq_u64 src;         // raw: the stream in the buffer
+  pq_u64 dst;         // the dense values' slot, 16-byte aligned, count * width bytes (unused for lengths)
+  pq_u32 src_size;
+  pq_u32 count;       // raw: the expected number of values
+  pq_u32 page;        // index into the page table (the offender word), or the stream's number
+  pq_u32 width;       // 4 or 8: the physical type's bytes; | QH_PQ_DS_LENGTHS for DELTA_LENGTH_BYTE_ARRAY
+} qh_pq_dstream;
+#define QH_PQ_DS_LENGTHS 0x100u
 
 // one compressed page (format level 2): k_pq_unsnap turns buffer[src .. src + src_size) into buffer[dst .. dst + dst_size)
 typedef struct qh_pq_unpack {
@@ -272,6 +325,24 @@ QH_PQ_HD inline void qh_pq_store(void* values, pq_u64 row, pq_u32 width, pq_u64 
     case 4: ((pq_u32*)values)[row] = (pq_u32)lo; break;
     case 8: ((pq_u64*)values)[row] = lo; break;
     default: ((pq_u64*)values)[2 * row] = lo; ((pq_u64*)values)[2 * row + 1] = hi; break;
+  }
+}
+
+// the same value out of a BYTE_STREAM_SPLIT region v of nn values: byte j of value idx lies at v[j * nn + idx]
+QH_PQ_HD inline void qh_pq_read_value_bss(const pq_u8* v, pq_u64 nn, pq_u64 idx, pq_u32 phys, pq_u32 flba, pq_u64* lo, pq_u64* hi) {
+  if (phys == QH_PQ_P_32) {
+    pq_u32 x = 0;
+    for (pq_u32 j = 0; j < 4; ++j) x |= (pq_u32)v[j * nn + idx] << (8 * j);
+    const pq_i64 s = (pq_i64)(int)x;
+    *lo = (pq_u64)s; *hi = s < 0 ? ~0ull : 0ull;
+  } else if (phys == QH_PQ_P_64) {
+    pq_u64 x = 0;
+    for (pq_u32 j = 0; j < 8; ++j) x |= (pq_u64)v[j * nn + idx] << (8 * j);
+    *lo = x; *hi = (x >> 63) ? ~0ull : 0ull;
+  } else {
+    pq_u64 l = (v[idx] & 0x80u) ? ~0ull : 0ull, h = l;
+    for (pq_u32 i = 0; i < flba; ++i) { h = (h << 8) | (l >> 56); l = (l << 8) | v[i * nn + idx]; }
+    *lo = l; *hi = h;
   }
 }
 

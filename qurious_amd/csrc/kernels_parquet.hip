@@ -7,7 +7,9 @@
 //   k_pq_unsnap   format level 2 only: a Snappy page of the uploaded chunks -> its uncompressed bytes in the unpack area
 //   k_pq_levels   RLE / bit-packed definition levels -> validity words, the page's non-NULL count, the column's NULL count
 //   k_pq_strings  the length chain of a Utf8 dictionary page or PLAIN data page, staged through LDS -> (length, position)
+//   k_pq_delta    encoding set 2 only: a DELTA_BINARY_PACKED stream -> dense values in the decoded area, or a Utf8 page's entries
 //   k_pq_values   64 rows per step: rank among the non-NULL rows -> value index -> run cursor -> dictionary gather or PLAIN read
+//   k_pq_values_ext  encoding set 2 only: the same body for RLE Boolean, BYTE_STREAM_SPLIT and DELTA_* pages
 //
 // Nothing here trusts the file: every run, index and length is checked against its stream, dictionary or page before it is
 // followed, and the first offender (page << 8 | reason) makes the whole call answer "needs host".
@@ -44,13 +46,15 @@ __global__ __launch_bounds__(QH_BLOCK) void k_pq_levels(const u8* __restrict__ b
     return;
   }
   const u8* p = buf + pg.pos;
+  const bool v2 = pg.flags & QH_PQ_F_V2;   // (encoding set 2: the stream lies at lev_pos, lev_size bytes the host has checked, no prefix)
   u32 reason = QH_PQ_OK, len = 0;
-  if (pg.size < 4) reason = QH_PQ_R_LEVELS_LENGTH;
+  if (v2) len = pg.lev_size;
+  else if (pg.size < 4) reason = QH_PQ_R_LEVELS_LENGTH;
   else {
     len = qh_pq_le32(p);
     if (len > pg.size - 4) reason = QH_PQ_R_LEVELS_LENGTH;
   }
-  const u8* s = p + 4;
+  const u8* s = v2 ? buf + pg.lev_pos : p + 4;
   u64 cpos = 0, row = 0;
   u32 nonnull = 0;
   qh_pq_run run;
@@ -81,7 +85,8 @@ __global__ __launch_bounds__(QH_BLOCK) void k_pq_levels(const u8* __restrict__ b
   const u32 total = (u32)qh_wave_sum_u64((u64)nonnull);
   if (lane == 0) {
     state[page].nonnull = total;
-    state[page].values_off = 4 + len;
+    state[page].values_off = v2 ? 0 : 4 + len;
+    if (!reason && v2 && n - (u64)total != (u64)pg.num_nulls) reason = QH_PQ_R_V2_NULLS;
     if (reason) pq_report(err, page, reason);
     else if (n > total) atomicAdd(&null_counts[pg.col], n - (u64)total);   // (one atomic per page)
   }
@@ -99,7 +104,7 @@ __global__ __launch_bounds__(64) void k_pq_strings(const u8* __restrict__ buf, u
   if (page >= npages) return;
   const qh_pq_page pg = pages[page];
   const qh_pq_col col = cols[pg.col];
-  if (col.phys != QH_PQ_P_BYTES || pg.enc == QH_PQ_ENC_DICT) return;
+  if (col.phys != QH_PQ_P_BYTES || pg.enc == QH_PQ_ENC_DICT || pg.enc == QH_PQ_ENC_DELTA_LEN) return;   // (k_pq_delta wrote a DELTA_LENGTH page's entries)
   if (__hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != ~0ULL) return;   // (the level pass found an offender: its state is void)
   const int lane = qh_lane();
   u64 base = pg.pos, size = pg.size, count = pg.num_values;
@@ -209,21 +214,30 @@ __global__ __launch_bounds__(64) void k_pq_unsnap(u8* buf, u64 buf_bytes, const 
 // page's running non-NULL count plus its rank in the step. Dictionary pages: a run cursor moves forward under wave-uniform
 // control until the step's highest index is inside or behind it; a lane whose index lies in the current run takes the RLE
 // value or extracts its bits.
-__global__ __launch_bounds__(QH_BLOCK) void k_pq_values(const u8* __restrict__ buf, const qh_pq_page* __restrict__ pages, u32 npages,
-                                                        const qh_pq_col* __restrict__ cols, const qh_pq_state* __restrict__ state, u64* err, u64* utf8_bytes) {
+//
+// Encoding set 2 adds a second instance of the same body, k_pq_values_ext, for the pages k_pq_values leaves alone: RLE Boolean
+// values (the run cursor at width 1, the "index" taken as the bit, no dictionary), BYTE_STREAM_SPLIT (one more gather),
+// DELTA_BINARY_PACKED (read as PLAIN from the slot k_pq_delta filled) and DELTA_LENGTH_BYTE_ARRAY (the entries k_pq_delta
+// wrote). It is launched only for a file that has such a page; kExt = false compiles to the kernel of encoding set 1.
+template <bool kExt>
+__device__ __forceinline__ void pq_values_body(const u8* __restrict__ buf, const qh_pq_page* __restrict__ pages, u32 npages, const qh_pq_col* __restrict__ cols,
+                                               const qh_pq_state* __restrict__ state, u64* err, u64* utf8_bytes) {
   const u32 page = (blockIdx.x * QH_BLOCK + threadIdx.x) >> 6;
   if (page >= npages) return;
   const qh_pq_page pg = pages[page];
-  if (pg.enc == QH_PQ_ENC_DICTPAGE) return;
+  if (kExt ? pg.enc < QH_PQ_ENC_RLE_BOOL : pg.enc >= QH_PQ_ENC_DICTPAGE) return;
   if (__hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != ~0ULL) return;   // (an earlier pass found an offender)
   const qh_pq_col col = cols[pg.col];
   const qh_pq_state st = state[page];
   const int lane = qh_lane();
   const u64 nn = st.nonnull;
-  const u8* v = buf + pg.pos + st.values_off;
-  const u64 vsize = (u64)pg.size - st.values_off;
   const u32 pw = qh_pq_phys_bytes(col.phys, col.flba);
+  const bool delta = kExt && pg.enc == QH_PQ_ENC_DELTA;   // (its nn dense values lie in its slot of the decoded area)
+  const u8* v = delta ? buf + pg.dict_pos : buf + pg.pos + st.values_off;
+  const u64 vsize = delta ? nn * pw : (u64)pg.size - st.values_off;
   const bool dict = pg.enc == QH_PQ_ENC_DICT;
+  const bool rleb = kExt && pg.enc == QH_PQ_ENC_RLE_BOOL, bss = kExt && pg.enc == QH_PQ_ENC_BSS;
+  const bool runs = dict || rleb;
   u32 reason = QH_PQ_OK, w = 0;
   const u8* s = v;
   u64 slen = 0;
@@ -235,6 +249,16 @@ __global__ __launch_bounds__(QH_BLOCK) void k_pq_values(const u8* __restrict__ b
         if (w > 32) reason = QH_PQ_R_BIT_WIDTH;
       }
     }
+  } else if (rleb) {
+    if (nn) {
+      if (vsize < 4) reason = QH_PQ_R_RLE_LENGTH;
+      else {
+        slen = qh_pq_le32(v); s = v + 4; w = 1;
+        if (slen > vsize - 4) reason = QH_PQ_R_RLE_LENGTH;
+      }
+    }
+  } else if (bss) {
+    if (nn * pw != vsize) reason = QH_PQ_R_BSS_SIZE;   // (no stride is guessed)
   } else if (col.phys == QH_PQ_P_BOOL) {
     if ((nn + 7) / 8 > vsize) reason = QH_PQ_R_VALUES_SHORT;
   } else if (col.phys != QH_PQ_P_BYTES) {
@@ -254,7 +278,7 @@ __global__ __launch_bounds__(QH_BLOCK) void k_pq_values(const u8* __restrict__ b
     base += (u64)__builtin_popcountll(m);
     if (base > nn) { reason = QH_PQ_R_VALUES_SHORT; break; }   // (cannot happen: the bitmap is what the level pass counted)
     u32 index = 0;
-    if (dict) {
+    if (runs) {
       bool served = !valid;
       for (;;) {
         if (!served && idx >= run.start && idx < run.start + run.count) { index = qh_pq_run_value(s, &run, idx, w); served = true; }
@@ -263,7 +287,8 @@ __global__ __launch_bounds__(QH_BLOCK) void k_pq_values(const u8* __restrict__ b
         if (reason) break;
       }
       if (reason) break;
-      if (qh_ballot(valid && index >= pg.dict_n)) { reason = QH_PQ_R_DICT_INDEX; break; }
+      if (dict && qh_ballot(valid && index >= pg.dict_n)) { reason = QH_PQ_R_DICT_INDEX; break; }
+      if (rleb && qh_ballot(valid && index > 1)) { reason = QH_PQ_R_RLE_LENGTH; break; }
     }
     u64 lo = 0, hi = 0, spos = 0;
     u32 slen_row = 0;
@@ -273,7 +298,9 @@ __global__ __launch_bounds__(QH_BLOCK) void k_pq_values(const u8* __restrict__ b
         const qh_pq_ent e = col.ent[pg.ent + (dict ? (u64)index : idx)];
         spos = e.pos; slen_row = e.len;
       } else if (col.phys == QH_PQ_P_BOOL) {
-        bit = (v[idx >> 3] >> (idx & 7)) & 1;
+        bit = rleb ? index != 0 : (v[idx >> 3] >> (idx & 7)) & 1;
+      } else if (bss) {
+        qh_pq_read_value_bss(v, nn, idx, col.phys, col.flba, &lo, &hi);
       } else {
         const u8* src = dict ? buf + pg.dict_pos + (u64)index * pw : v + idx * pw;
         qh_pq_read_value(src, col.phys, col.flba, &lo, &hi);
@@ -296,7 +323,153 @@ __global__ __launch_bounds__(QH_BLOCK) void k_pq_values(const u8* __restrict__ b
   }
 }
 
+__global__ __launch_bounds__(QH_BLOCK) void k_pq_values(const u8* __restrict__ buf, const qh_pq_page* __restrict__ pages, u32 npages,
+                                                        const qh_pq_col* __restrict__ cols, const qh_pq_state* __restrict__ state, u64* err, u64* utf8_bytes) {
+  pq_values_body<false>(buf, pages, npages, cols, state, err, utf8_bytes);
+}
+__global__ __launch_bounds__(QH_BLOCK) void k_pq_values_ext(const u8* __restrict__ buf, const qh_pq_page* __restrict__ pages, u32 npages,
+                                                            const qh_pq_col* __restrict__ cols, const qh_pq_state* __restrict__ state, u64* err, u64* utf8_bytes) {
+  pq_values_body<true>(buf, pages, npages, cols, state, err, utf8_bytes);
+}
+
+__device__ __forceinline__ u64 pq_shfl_up64(u64 v, int d) {
+  const u32 lo = (u32)__shfl_up((int)(u32)v, d, 64), hi = (u32)__shfl_up((int)(u32)(v >> 32), d, 64);
+  return ((u64)hi << 32) | lo;
+}
+__device__ __forceinline__ u64 pq_incl_scan64(u64 v, int lane) {
+  for (int d = 1; d < 64; d <<= 1) { const u64 t = pq_shfl_up64(v, d); if (lane >= d) v += t; }
+  return v;
+}
+__device__ __forceinline__ u64 pq_lane63(u64 v) {
+  return ((u64)(u32)__shfl((int)(u32)(v >> 32), 63, 64) << 32) | (u32)__shfl((int)(u32)v, 63, 64);
+}
+
+// Encoding set 2: one wavefront (a workgroup of its own) per DELTA_BINARY_PACKED stream (device/qhip_delta.inc). The walk over
+// the stream header and the block headers is serial and wave-uniform: every lane parses the same bytes. The values are taken 64
+// per step: a step lies in one block and touches at most two miniblocks (a miniblock holds a multiple of 32 values), whose
+// widths and byte positions every lane knows; lane l extracts delta k0 + l with byte loads of its own miniblock, adds the
+// block's min delta, the wavefront scans (six rounds of __shfl_up on 64-bit values: the sums wrap mod 2^64, and a 4-byte type
+// keeps the low half, which is the sum mod 2^32), the step's carry is added and lane 63's value is the next carry.
+// A stream of a page (pages != NULL) is where the level pass says the values begin and has the page's non-NULL count; a raw
+// stream (qhip_parquet_delta_decode) is what its table entry says. Dense values go to the stream's slot, from where
+// k_pq_values_ext reads the page as PLAIN. The lengths of DELTA_LENGTH_BYTE_ARRAY get a second scan and become the page's
+// (length, position) entries, what k_pq_strings writes for a PLAIN page: the bytes begin where the length stream ends, which is
+// known only behind the last block, so the positions are written relative to it and every lane moves the entries it wrote
+// itself (entry i > 0 belongs to lane (i - 1) & 63: a block is a multiple of 128 values) once the walk is over.
+// Every loop advances by a block that holds a value and at least one byte, or by 64 values of it: bounded by the count, which
+// the page's rows bound, and by the stream's bytes. A refused stream leaves its slot half written; nobody reads it.
+__global__ __launch_bounds__(64) void k_pq_delta(u8* buf, const qh_pq_dstream* __restrict__ tab, u32 n, const qh_pq_page* __restrict__ pages,
+                                                 const qh_pq_col* __restrict__ cols, const qh_pq_state* __restrict__ state, u64* err, u32* status, u64* ends) {
+  const u32 k = blockIdx.x;
+  if (k >= n) return;
+  const qh_pq_dstream t = tab[k];
+  const int lane = qh_lane();
+  u64 src = t.src, size = t.src_size, count = t.count;
+  const bool lengths = t.width & QH_PQ_DS_LENGTHS;
+  const u32 width = t.width & 0xFFu, bits = width * 8;
+  qh_pq_ent* ent = nullptr;
+  if (pages) {
+    if (__hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != ~0ULL) return;   // (the level pass found an offender: its state is void)
+    const qh_pq_page pg = pages[t.page];
+    const qh_pq_state st = state[t.page];
+    src = pg.pos + st.values_off; size = (u64)pg.size - st.values_off; count = st.nonnull;
+    if (!count) return;   // (a page without non-NULL rows is not looked at beyond its levels)
+    if (lengths) ent = cols[pg.col].ent + pg.ent;
+  }
+  const u8* s = buf + src;
+  u8* out = buf + t.dst;
+  qh_dl_head h;
+  u32 reason = (u32)qh_dl_header(s, size, &h);
+  if (!reason && (u64)h.total != count) reason = QH_PQ_R_DELTA_COUNT;
+  u64 pos = 0, carry = 0, produced = 0, sum = 0;   // sum (lengths): bytes of the values so far
+  if (!reason) {
+    pos = h.end;
+    if (count) {
+      carry = h.first; produced = 1;
+      if (lengths) {
+        if ((int)(u32)carry < 0) reason = QH_PQ_R_DELTA_LENGTH;
+        else if (lane == 0) { qh_pq_ent e; e.pos = 0; e.len = (u32)carry; e.pad = 0; ent[0] = e; }
+        sum = (u32)carry;
+      } else if (lane == 0) {
+        if (width == 4) ((u32*)out)[0] = (u32)carry; else ((u64*)out)[0] = carry;
+      }
+    }
+  }
+  while (!reason && produced < count) {
+    u64 min_delta = 0, wat = 0, at = 0;
+    reason = (u32)qh_dl_block(s, size, pos, h.mpb, &min_delta, &wat, &at);
+    if (reason) break;
+    const u64 left = count - produced, in_block = left < (u64)h.block ? left : (u64)h.block;
+    const u64 mbytes = h.vpm >> 3;   // bytes of a miniblock per bit of width
+    u32 cur_m = 0, cur_w = s[wat];
+    reason = (u32)qh_dl_miniblock(cur_w, bits, h.vpm, size - at);
+    for (u64 k0 = 0; !reason && k0 < in_block; k0 += 64) {
+      const u64 last = k0 + 63 < in_block ? k0 + 63 : in_block - 1;
+      const u32 m_lo = (u32)(k0 / h.vpm), m_hi = (u32)(last / h.vpm);
+      if (m_lo != cur_m) {   // the step before ended with its miniblock
+        at += mbytes * cur_w; cur_m = m_lo; cur_w = s[wat + cur_m];
+        reason = (u32)qh_dl_miniblock(cur_w, bits, h.vpm, size - at);
+        if (reason) break;
+      }
+      u64 next_at = 0;
+      u32 next_w = 0;
+      if (m_hi != m_lo) {
+        next_at = at + mbytes * cur_w; next_w = s[wat + m_hi];
+        reason = (u32)qh_dl_miniblock(next_w, bits, h.vpm, size - next_at);
+        if (reason) break;
+      }
+      const u64 v = k0 + (u64)lane;
+      const bool active = v <= last;
+      u64 x = 0;
+      if (active) {
+        const u32 mi = (u32)(v / h.vpm);
+        const u64 kk = v - (u64)mi * h.vpm;
+        x = (mi == m_lo ? qh_dl_extract(s + at, kk, cur_w) : qh_dl_extract(s + next_at, kk, next_w)) + min_delta;
+      }
+      const u64 val = carry + pq_incl_scan64(x, lane);
+      carry = pq_lane63(val);   // (an idle lane adds 0: lane 63 holds the step's last value)
+      if (lengths) {
+        const u32 len = (u32)val;
+        if (qh_ballot(active && (int)len < 0)) { reason = QH_PQ_R_DELTA_LENGTH; break; }
+        const u64 incl = pq_incl_scan64(active ? (u64)len : 0, lane);
+        if (active) { qh_pq_ent e; e.pos = sum + incl - len; e.len = len; e.pad = 0; ent[produced + v] = e; }
+        sum += pq_lane63(incl);
+      } else if (active) {
+        if (width == 4) ((u32*)out)[produced + v] = (u32)val; else ((u64*)out)[produced + v] = val;
+      }
+      if (m_hi != m_lo) { at = next_at; cur_w = next_w; cur_m = m_hi; }
+    }
+    if (reason) break;
+    pos = at + mbytes * cur_w;   // (the last miniblock that holds a value is stored whole)
+    produced += in_block;
+  }
+  if (!reason && lengths) {
+    if (sum > size - pos) reason = QH_PQ_R_DELTA_LENGTH;
+    else {
+      const u64 base = src + pos;
+      if (lane == 0) ent[0].pos = base;
+      for (u64 i = 1 + (u64)lane; i < count; i += 64) ent[i].pos += base;
+    }
+  }
+  if (lane == 0) {
+    if (status) status[k] = reason;
+    if (ends) ends[k] = pos;
+    if (reason && err) pq_report(err, t.page, reason);
+  }
+}
+
 // ---------------------------------------------------------------- launchers
+void launch_pq_delta(uint8_t* buf, const qh_pq_dstream* tab, uint32_t n, const qh_pq_page* pages, const qh_pq_col* cols, const qh_pq_state* state, uint64_t* err,
+                     uint32_t* status, uint64_t* ends, hipStream_t s) {
+  if (!n) return;
+  hipLaunchKernelGGL(k_pq_delta, dim3(n), dim3(64), 0, s, (u8*)buf, tab, (u32)n, pages, cols, state, (u64*)err, (u32*)status, (u64*)ends);
+}
+void launch_pq_values_ext(const uint8_t* buf, const qh_pq_page* pages, uint32_t npages, const qh_pq_col* cols, const qh_pq_state* state, uint64_t* err,
+                          uint64_t* utf8_bytes, hipStream_t s) {
+  if (!npages) return;
+  const unsigned g = (unsigned)(((uint64_t)npages * 64 + QH_BLOCK - 1) / QH_BLOCK);
+  hipLaunchKernelGGL(k_pq_values_ext, dim3(g), dim3(QH_BLOCK), 0, s, (const u8*)buf, pages, (u32)npages, cols, state, (u64*)err, (u64*)utf8_bytes);
+}
 void launch_pq_levels(const uint8_t* buf, const qh_pq_page* pages, uint32_t npages, const qh_pq_col* cols, qh_pq_state* state, uint64_t* err, uint64_t* null_counts,
                       hipStream_t s) {
   if (!npages) return;

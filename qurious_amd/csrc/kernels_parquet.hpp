@@ -5,8 +5,19 @@
 #include <cstdint>
 
 #include "device/qhip_parquet.inc"
+#include "device/qhip_delta.inc"
 
 namespace qhip {
+
+// encoding set 2: the n DELTA_BINARY_PACKED streams of `tab`, one wavefront each. pages / cols / state not NULL: streams of
+// pages, behind the level pass (dense values into their slots of the decoded area, DELTA_LENGTH_BYTE_ARRAY lengths into the
+// column's entries). pages NULL: raw streams. err / status / ends (each may be NULL): the first offender; per stream its reason
+// and the byte position where it ended.
+void launch_pq_delta(uint8_t* buf, const qh_pq_dstream* tab, uint32_t n, const qh_pq_page* pages, const qh_pq_col* cols, const qh_pq_state* state, uint64_t* err,
+                     uint32_t* status, uint64_t* ends, hipStream_t s);
+// encoding set 2: k_pq_values' body for the pages it leaves alone (RLE Boolean, BYTE_STREAM_SPLIT, DELTA_*)
+void launch_pq_values_ext(const uint8_t* buf, const qh_pq_page* pages, uint32_t npages, const qh_pq_col* cols, const qh_pq_state* state, uint64_t* err,
+                          uint64_t* utf8_bytes, hipStream_t s);
 
 // format level 2: the n Snappy streams of `tab` (positions in buf, of buf_bytes bytes plus the allocation's slack), one wavefront
 // each, unpacked into their slots. err (may be NULL): the smallest (page << 8 | reason), ~0 when none. status (may be NULL):

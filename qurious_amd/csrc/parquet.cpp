@@ -6,15 +6,19 @@
 // PCIe — and the device turns pages into columns. Format level 1: uncompressed chunks, data pages V1, PLAIN and dictionary
 // encodings, RLE definition levels, flat columns. Format level 2 (qhip_ctx_set_parquet_format) adds SNAPPY chunks: their pages
 // are uploaded compressed and unpacked on the device into an unpack area behind the uploaded chunks in the same buffer, where
-// the passes below read them as they read any page. Whatever lies outside makes the whole call answer QHIP_UNSUPPORTED with nothing
+// the passes below read them as they read any page. Encoding set 2 (qhip_ctx_set_parquet_encodings), independent of the level,
+// adds data pages V2, RLE Boolean values, BYTE_STREAM_SPLIT, DELTA_BINARY_PACKED and DELTA_LENGTH_BYTE_ARRAY: a pass in front
+// (k_pq_delta) leaves a delta page's values dense in a decoded area behind the unpack area. Whatever lies outside makes the whole call answer QHIP_UNSUPPORTED with nothing
 // created, and the caller takes the host path, which then produces every error message.
 //
 // Passes, all on the context's stream:
 //   1 upload        the projected chunks, one behind the other, into one device buffer; the page table and column descriptors
 //  (k_pq_unsnap    level 2, a file with Snappy pages only: one wavefront per page, into the unpack area)
 //   2 k_pq_levels   definition levels -> validity words, non-NULL count per page, NULL count per column
+//  (k_pq_delta     set 2, a file with DELTA_* pages only: one wavefront per page, into the decoded area or the column's entries)
 //   3 k_pq_strings  Utf8: the length chains of dictionary pages and PLAIN data pages -> (length, position) entries
 //   4 k_pq_values   values: bit-unpack, dictionary gather, scatter over NULLs; Utf8 rows get (length, position)
+//  (k_pq_values_ext set 2, a file with RLE Boolean, BYTE_STREAM_SPLIT or DELTA_* pages only: the same body for those pages)
 //                   -> the ONE host wait: first offender, NULL counts, Utf8 byte totals (they size the data buffers)
 //   5 Utf8          lengths scanned in place into offsets, k_csv_copy_utf8 moves the bytes (no wait: stream-ordered)
 #include <hip/hip_runtime_api.h>
@@ -27,7 +31,8 @@
 
 namespace qhip {
 
-static_assert(sizeof(qh_pq_page) == 56 && sizeof(qh_pq_col) == 48 && sizeof(qh_pq_ent) == 16, "the Parquet descriptors have the layout both compilers agree on");
+static_assert(sizeof(qh_pq_dstream) == 32, "the delta-table entry has the layout both compilers agree on");
+static_assert(sizeof(qh_pq_page) == 80 && sizeof(qh_pq_col) == 48 && sizeof(qh_pq_ent) == 16, "the Parquet descriptors have the layout both compilers agree on");
 static_assert(sizeof(qh_pq_unpack) == 32, "the unpack-table entry has the layout both compilers agree on");
 
 qhip_table* table_from_parquet(Ctx* ctx, const ArrowSchema* schema, const uint8_t* bytes, int64_t n_bytes, const int32_t* columns, int32_t n_columns,
@@ -63,7 +68,7 @@ qhip_table* table_from_parquet(Ctx* ctx, const ArrowSchema* schema, const uint8_
   // ---- footer and page walk (host, one header per page)
   qhip_pq::Plan plan;
   try {
-    plan = qhip_pq::plan_file(bytes, (uint64_t)n_bytes, &names, types, proj, ctx->parquet_format);
+    plan = qhip_pq::plan_file(bytes, (uint64_t)n_bytes, &names, types, proj, ctx->parquet_format, ctx->parquet_encodings);
   } catch (const qhip_pq::PqNeedsHost& e) {
     fail(QHIP_UNSUPPORTED, qhip_pq::needs_host_text(e));
   }
@@ -84,8 +89,9 @@ qhip_table* table_from_parquet(Ctx* ctx, const ArrowSchema* schema, const uint8_
   ctx->wide_join_stage_ms = 0;
   for (float& ms : ctx->parquet_pass_ms) ms = 0;
   ctx->parquet_unpack_ms = 0;
-  hipEvent_t ev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // ([6]: behind the unpack pass)
-  struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int k = 0; k < 7; ++k) if (e[k]) (void)hipEventDestroy(e[k]); } } ev_guard{ev};
+  ctx->parquet_delta_ms = 0;
+  hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // ([6]: behind the unpack pass, [7]: behind the delta pass)
+  struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int k = 0; k < 8; ++k) if (e[k]) (void)hipEventDestroy(e[k]); } } ev_guard{ev};
   auto mark = [&](int k) {
     if (!ctx->timing) return;
     if (!ev[k]) QHIP_HIP_CHECK(hipEventCreate(&ev[k]));
@@ -95,7 +101,7 @@ qhip_table* table_from_parquet(Ctx* ctx, const ArrowSchema* schema, const uint8_
   mark(0);
 
   // ---- 1. upload: the projected chunks only (the buffer keeps the 64 bytes of slack DevBuf::alloc gives); behind them the
-  // unpack area of a file with Snappy pages, which nothing uploads
+  // unpack area of a file with Snappy pages and the decoded area of one with DELTA_BINARY_PACKED pages, which nothing uploads
   const uint64_t buf_bytes = plan.buffer_bytes();
   const uint32_t nunpack = (uint32_t)plan.unpack.size();
   DevBuf file((size_t)buf_bytes);
@@ -150,6 +156,10 @@ qhip_table* table_from_parquet(Ctx* ctx, const ArrowSchema* schema, const uint8_
   DevBuf unpack_d;
   if (nunpack) unpack_d.alloc((size_t)nunpack * sizeof(qh_pq_unpack));
   if (nunpack) QHIP_HIP_CHECK(hipMemcpyAsync(unpack_d.ptr, plan.unpack.data(), (size_t)nunpack * sizeof(qh_pq_unpack), hipMemcpyHostToDevice, ctx->stream));
+  const uint32_t ndelta = (uint32_t)plan.delta.size();
+  DevBuf delta_d;
+  if (ndelta) delta_d.alloc((size_t)ndelta * sizeof(qh_pq_dstream));
+  if (ndelta) QHIP_HIP_CHECK(hipMemcpyAsync(delta_d.ptr, plan.delta.data(), (size_t)ndelta * sizeof(qh_pq_dstream), hipMemcpyHostToDevice, ctx->stream));
   mark(1);
 
   // ---- level 2: the Snappy pages into their slots
@@ -162,9 +172,17 @@ qhip_table* table_from_parquet(Ctx* ctx, const ArrowSchema* schema, const uint8_
   // ---- 2 .. 4: levels, string walk, values
   launch_pq_levels(file.as<uint8_t>(), pages_d.as<qh_pq_page>(), npages, cols_d.as<qh_pq_col>(), state_d.as<qh_pq_state>(), st_dev, st_dev + 1, ctx->stream);
   mark(2);
+  if (ndelta) {   // (behind the levels: a page's stream begins where they end and holds its non-NULL rows)
+    launch_pq_delta(file.as<uint8_t>(), delta_d.as<qh_pq_dstream>(), ndelta, pages_d.as<qh_pq_page>(), cols_d.as<qh_pq_col>(), state_d.as<qh_pq_state>(), st_dev, nullptr,
+                    nullptr, ctx->stream);
+    mark(7);
+  }
   launch_pq_strings(file.as<uint8_t>(), buf_bytes, pages_d.as<qh_pq_page>(), npages, cols_d.as<qh_pq_col>(), state_d.as<qh_pq_state>(), st_dev, ctx->stream);
   mark(3);
   launch_pq_values(file.as<uint8_t>(), pages_d.as<qh_pq_page>(), npages, cols_d.as<qh_pq_col>(), state_d.as<qh_pq_state>(), st_dev, st_dev + 1 + QH_PQ_MAX_COLS, ctx->stream);
+  if (plan.has_ext)
+    launch_pq_values_ext(file.as<uint8_t>(), pages_d.as<qh_pq_page>(), npages, cols_d.as<qh_pq_col>(), state_d.as<qh_pq_state>(), st_dev, st_dev + 1 + QH_PQ_MAX_COLS,
+                         ctx->stream);
   time_mark(ctx, 3);
   mark(4);
   std::vector<uint64_t> back(st_host.size());
@@ -202,6 +220,10 @@ qhip_table* table_from_parquet(Ctx* ctx, const ArrowSchema* schema, const uint8_
     if (ev[6]) {   // "levels" begins behind the unpack pass, "upload" stays the upload
       (void)hipEventElapsedTime(&ctx->parquet_unpack_ms, ev[1], ev[6]);
       (void)hipEventElapsedTime(&ctx->parquet_pass_ms[1], ev[6], ev[2]);
+    }
+    if (ev[7]) {   // ... and the "string walk" behind the delta pass
+      (void)hipEventElapsedTime(&ctx->parquet_delta_ms, ev[2], ev[7]);
+      (void)hipEventElapsedTime(&ctx->parquet_pass_ms[2], ev[7], ev[3]);
     }
   }
   time_mark(ctx, 1);
@@ -273,6 +295,57 @@ void snappy_decode(Ctx* ctx, const uint8_t* bytes, int64_t n_bytes, const int64_
   }
 }
 
+// qhip_parquet_delta_decode: k_pq_delta over raw DELTA_BINARY_PACKED streams. A refused stream is an answer (status), not an error.
+void delta_decode(Ctx* ctx, const uint8_t* bytes, int64_t n_bytes, const int64_t* src_offsets, const int32_t* widths, const int64_t* counts, int64_t n_streams,
+                  uint8_t* out, int64_t out_bytes, int64_t* end_pos, int32_t* status) {
+  uint64_t total_out = 0;
+  for (int64_t k = 0; k < n_streams; ++k) {
+    const int64_t a = src_offsets[k], b = src_offsets[k + 1];
+    if (a < 0 || b < a || b > n_bytes || b - a > 0x7FFFFFFF || counts[k] < 0 || counts[k] > 0x0FFFFFFF || (widths[k] != 4 && widths[k] != 8))
+      fail(QHIP_INVALID_ARGUMENT, "qhip_parquet_delta_decode: stream " + std::to_string(k) + " lies outside the bytes, its count is negative or above 2^28 - 1, or its width is not 4 or 8");
+    total_out += (uint64_t)counts[k] * (uint64_t)widths[k];
+  }
+  if (total_out > (uint64_t)out_bytes) fail(QHIP_INVALID_ARGUMENT, "qhip_parquet_delta_decode: out is smaller than the sum of counts times widths");
+  ctx->parquet_delta_ms = 0;
+  if (!n_streams) return;
+  const uint64_t base = ((uint64_t)n_bytes + 15) & ~(uint64_t)15;
+  uint64_t area = 0;
+  std::vector<qh_pq_dstream> tab((size_t)n_streams);
+  for (int64_t k = 0; k < n_streams; ++k) {
+    qh_pq_dstream& d = tab[(size_t)k];
+    memset(&d, 0, sizeof d);
+    d.src = (uint64_t)src_offsets[k]; d.src_size = (uint32_t)(src_offsets[k + 1] - src_offsets[k]);
+    d.dst = base + area; d.count = (uint32_t)counts[k]; d.page = (uint32_t)k; d.width = (uint32_t)widths[k];
+    area += ((uint64_t)d.count * d.width + 15) & ~(uint64_t)15;
+  }
+  QHIP_HIP_CHECK(hipSetDevice(ctx->device));
+  const uint32_t nt = (uint32_t)n_streams;
+  DevBuf buf((size_t)(base + area)), tab_d((size_t)nt * sizeof(qh_pq_dstream)), st_d((size_t)nt * 4), end_d((size_t)nt * 8);
+  if (n_bytes) QHIP_HIP_CHECK(hipMemcpyAsync(buf.ptr, bytes, (size_t)n_bytes, hipMemcpyHostToDevice, ctx->stream));
+  QHIP_HIP_CHECK(hipMemcpyAsync(tab_d.ptr, tab.data(), (size_t)nt * sizeof(qh_pq_dstream), hipMemcpyHostToDevice, ctx->stream));
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int k = 0; k < 2; ++k) if (e[k]) (void)hipEventDestroy(e[k]); } } ev_guard{ev};
+  if (ctx->timing) { QHIP_HIP_CHECK(hipEventCreate(&ev[0])); QHIP_HIP_CHECK(hipEventCreate(&ev[1])); QHIP_HIP_CHECK(hipEventRecord(ev[0], ctx->stream)); }
+  launch_pq_delta(buf.as<uint8_t>(), tab_d.as<qh_pq_dstream>(), nt, nullptr, nullptr, nullptr, nullptr, st_d.as<uint32_t>(), end_d.as<uint64_t>(), ctx->stream);
+  if (ctx->timing) QHIP_HIP_CHECK(hipEventRecord(ev[1], ctx->stream));
+  std::vector<uint8_t> dense((size_t)area);
+  std::vector<uint32_t> st(nt);
+  std::vector<uint64_t> ends(nt);
+  if (area) QHIP_HIP_CHECK(hipMemcpyAsync(dense.data(), (const uint8_t*)buf.ptr + base, (size_t)area, hipMemcpyDeviceToHost, ctx->stream));
+  QHIP_HIP_CHECK(hipMemcpyAsync(ends.data(), end_d.ptr, (size_t)nt * 8, hipMemcpyDeviceToHost, ctx->stream));
+  copy_sync(ctx->stream, st.data(), st_d.ptr, (size_t)nt * 4, hipMemcpyDeviceToHost);
+  if (ctx->timing) (void)hipEventElapsedTime(&ctx->parquet_delta_ms, ev[0], ev[1]);
+  uint64_t at = 0;
+  for (uint32_t i = 0; i < nt; ++i) {
+    const qh_pq_dstream& d = tab[i];
+    const uint64_t nb = (uint64_t)d.count * d.width;
+    status[i] = (int32_t)st[i];
+    end_pos[i] = st[i] ? -1 : (int64_t)ends[i];
+    if (!st[i] && nb) memcpy(out + at, dense.data() + (d.dst - base), (size_t)nb);
+    at += nb;
+  }
+}
+
 }  // namespace qhip
 
 using namespace qhip;
@@ -296,6 +369,20 @@ int qhip_ctx_parquet_unpack_ms(const qhip_ctx* ctx, double* out) {
   if (!ctx || !out) return QHIP_INVALID_ARGUMENT;
   *out = (double)ctx->parquet_unpack_ms;
   return QHIP_OK;
+}
+
+int qhip_ctx_parquet_delta_ms(const qhip_ctx* ctx, double* out) {
+  if (!ctx || !out) return QHIP_INVALID_ARGUMENT;
+  *out = (double)ctx->parquet_delta_ms;
+  return QHIP_OK;
+}
+
+int qhip_parquet_delta_decode(qhip_ctx* ctx, const void* bytes, int64_t n_bytes, const int64_t* src_offsets, const int32_t* widths, const int64_t* counts,
+                              int64_t n_streams, void* out, int64_t out_bytes, int64_t* end_pos, int32_t* status) {
+  if (!ctx || n_bytes < 0 || (n_bytes > 0 && !bytes) || n_streams < 0 || out_bytes < 0 || (out_bytes > 0 && !out)) return QHIP_INVALID_ARGUMENT;
+  if (n_streams > 0 && (!src_offsets || !widths || !counts || !end_pos || !status)) return QHIP_INVALID_ARGUMENT;
+  if (n_streams >= (1 << 24)) return QHIP_INVALID_ARGUMENT;
+  return guarded(ctx, [&] { delta_decode(ctx, (const uint8_t*)bytes, n_bytes, src_offsets, widths, counts, n_streams, (uint8_t*)out, out_bytes, end_pos, status); });
 }
 
 int qhip_snappy_decode(qhip_ctx* ctx, const void* bytes, int64_t n_bytes, const int64_t* src_offsets, const int64_t* dst_sizes, int64_t n_streams, void* out,

@@ -2,7 +2,8 @@
 // tests/cpp/parquet_tests.cpp, which runs it under the sanitizers): a bounds-checked Thrift compact-protocol reader, the footer
 // (FileMetaData) and page headers decoded as far as they are used, the match of a column's physical type and annotation against
 // its Arrow type, and the page walk that turns the projected chunks into a page table and, at format level 2, the pages of Snappy
-// chunks into an unpack table with their slots in the unpack area. Plain C++, no Arrow, no HIP.
+// chunks into an unpack table with their slots in the unpack area and, at encoding set 2, data pages V2 and the DELTA_* pages into
+// a delta table with their slots in the decoded area. Plain C++, no Arrow, no HIP.
 // Every offset, length and count comes from the file and is checked before it is followed: a violation throws PqNeedsHost.
 #pragma once
 #include <cstdint>
@@ -13,10 +14,11 @@
 #include "qhip.h"
 #include "device/qhip_parquet.inc"
 #include "device/qhip_snappy.inc"
+#include "device/qhip_delta.inc"
 
 static_assert(QH_PQ_R_SNAPPY_PREAMBLE == QH_PQ_R_SNAPPY_BASE + QH_SNAP_E_PREAMBLE && QH_PQ_R_SNAPPY_OFFSET == QH_PQ_R_SNAPPY_BASE + QH_SNAP_E_OFFSET &&
-                  QH_PQ_R_COUNT == QH_PQ_R_SNAPPY_BASE + QH_SNAP_E_COUNT,
-              "the Snappy reasons follow the decoder's error codes");
+                  QH_PQ_R_V2_UNCOMPRESSED == QH_PQ_R_SNAPPY_BASE + QH_SNAP_E_COUNT,
+              "the Snappy reasons follow the decoder's error codes, the reasons of encoding set 2 follow them");
 
 namespace qhip_pq {
 
@@ -116,7 +118,8 @@ struct Thrift {
 
 // ---------------------------------------------------------------- the parts of the metadata that are used
 enum { PT_BOOLEAN = 0, PT_INT32 = 1, PT_INT64 = 2, PT_INT96 = 3, PT_FLOAT = 4, PT_DOUBLE = 5, PT_BYTE_ARRAY = 6, PT_FLBA = 7 };
-enum { ENC_PLAIN = 0, ENC_PLAIN_DICTIONARY = 2, ENC_RLE = 3, ENC_BIT_PACKED = 4, ENC_RLE_DICTIONARY = 8 };
+enum { ENC_PLAIN = 0, ENC_PLAIN_DICTIONARY = 2, ENC_RLE = 3, ENC_BIT_PACKED = 4, ENC_DELTA_BINARY_PACKED = 5, ENC_DELTA_LENGTH_BYTE_ARRAY = 6, ENC_DELTA_BYTE_ARRAY = 7,
+       ENC_RLE_DICTIONARY = 8, ENC_BYTE_STREAM_SPLIT = 9 };
 enum { PAGE_DATA = 0, PAGE_INDEX = 1, PAGE_DICTIONARY = 2, PAGE_DATA_V2 = 3 };
 enum { CODEC_UNCOMPRESSED = 0, CODEC_SNAPPY = 1 };
 enum { L_NONE = 0, L_STRING, L_DECIMAL, L_DATE, L_TIMESTAMP, L_INT, L_OTHER };
@@ -140,6 +143,9 @@ struct PageHeader {
   int64_t uncompressed = -1, compressed = -1;
   bool has_data = false, has_dict = false;
   int64_t num_values = -1, encoding = -1, def_encoding = -1;   // of the data or dictionary page header
+  // DataPageHeaderV2 (read at encoding set 2 only): its num_values and encoding stand above where the page's type is DATA_PAGE_V2
+  bool has_v2 = false, is_compressed = true;
+  int64_t num_nulls = -1, num_rows = -1, def_bytes = -1, rep_bytes = -1;
   uint64_t header_bytes = 0;
 };
 
@@ -259,10 +265,12 @@ inline Footer read_footer(const uint8_t* bytes, uint64_t len) {
   return f;
 }
 
-// one page header in bytes[0 .. len): nothing behind len is read
-inline PageHeader read_page_header(const uint8_t* bytes, uint64_t len) {
+// one page header in bytes[0 .. len): nothing behind len is read. v2: decode DataPageHeaderV2 as well (else it is skipped); a
+// page of another type that carries one too is answered as without it
+inline PageHeader read_page_header(const uint8_t* bytes, uint64_t len, bool v2 = false) {
   Thrift t(bytes, len);
   PageHeader h;
+  int64_t v2_num_values = -1, v2_encoding = -1;
   int last = 0, id, ty;
   while (t.field(last, id, ty)) {
     if (id == 1) h.type = (int)t.integer(ty);
@@ -277,8 +285,24 @@ inline PageHeader read_page_header(const uint8_t* bytes, uint64_t len) {
         else if (id2 == 3 && id == 5) h.def_encoding = t.integer(ty2);
         else t.skip(ty2, 2);   // (Statistics, is_sorted, the repetition level encoding: a flat column has none)
       }
+    } else if (v2 && id == 8 && ty == T_STRUCT) {
+      h.has_v2 = true;
+      int l2 = 0, id2, ty2;
+      while (t.field(l2, id2, ty2)) {
+        switch (id2) {
+          case 1: v2_num_values = t.integer(ty2); break;
+          case 2: h.num_nulls = t.integer(ty2); break;
+          case 3: h.num_rows = t.integer(ty2); break;
+          case 4: v2_encoding = t.integer(ty2); break;
+          case 5: h.def_bytes = t.integer(ty2); break;
+          case 6: h.rep_bytes = t.integer(ty2); break;
+          case 7: h.is_compressed = t.boolean(ty2); break;
+          default: t.skip(ty2, 2); break;   // (Statistics)
+        }
+      }
     } else t.skip(ty, 1);
   }
+  if (h.has_v2 && h.type == PAGE_DATA_V2) { h.num_values = v2_num_values; h.encoding = v2_encoding; }
   h.header_bytes = t.pos;
   return h;
 }
@@ -339,13 +363,23 @@ struct Plan {
   // unpack_base) the unpack area: one 16-byte aligned slot of uncompressed_page_size bytes per entry. Empty at level 1.
   std::vector<qh_pq_unpack> unpack;
   uint64_t unpack_base = 0, unpack_bytes = 0;
-  uint64_t buffer_bytes() const { return unpack.empty() ? upload_bytes : unpack_base + unpack_bytes; }
+  // encoding set 2: the DELTA_BINARY_PACKED pages (k_pq_delta). The dense values of one get a 16-byte aligned slot of
+  // num_values x width bytes in the decoded area, which lies behind the unpack area (at decoded_base) in the same buffer;
+  // DELTA_LENGTH_BYTE_ARRAY lengths become entries of their column and need no slot. has_ext: some page is for k_pq_values_ext.
+  std::vector<qh_pq_dstream> delta;
+  uint64_t decoded_base = 0, decoded_bytes = 0;
+  bool has_ext = false;
+  uint64_t packed_bytes() const { return unpack.empty() ? upload_bytes : unpack_base + unpack_bytes; }
+  uint64_t buffer_bytes() const { return decoded_bytes ? decoded_base + decoded_bytes : packed_bytes(); }
 };
 
 // names: the schema's field names (checked against the file's when given). types: the Arrow type of EVERY field. proj: the
-// fields to decode, in output order. level: the format level (qhip_ctx_set_parquet_format); 2 admits SNAPPY chunks.
+// fields to decode, in output order. level: the format level (qhip_ctx_set_parquet_format); 2 admits SNAPPY chunks. encodings:
+// the encoding set (qhip_ctx_set_parquet_encodings); 2 admits data pages V2, RLE Boolean values, BYTE_STREAM_SPLIT,
+// DELTA_BINARY_PACKED and DELTA_LENGTH_BYTE_ARRAY. At set 1 nothing below differs from what it was before the set existed.
 inline Plan plan_file(const uint8_t* file, uint64_t n, const std::vector<std::string>* names, const std::vector<ArrowType>& types, const std::vector<int32_t>& proj,
-                      int level = 1) {
+                      int level = 1, int encodings = 1) {
+  const bool set2 = encodings >= 2;
   if (n >= 4 && memcmp(file, "PARE", 4) == 0) needs_host(QH_PQ_R_ENCRYPTED);
   if (n >= 4 && memcmp(file + n - 4, "PARE", 4) == 0) needs_host(QH_PQ_R_ENCRYPTED);
   if (n < 12 || memcmp(file, "PAR1", 4) != 0 || memcmp(file + n - 4, "PAR1", 4) != 0) needs_host(QH_PQ_R_MAGIC);
@@ -410,13 +444,14 @@ inline Plan plan_file(const uint8_t* file, uint64_t n, const std::vector<std::st
       plan.upload_bytes += cbytes;
       const uint8_t* chunk = file + start;
       const uint32_t pw = qh_pq_phys_bytes(cp.phys, cp.flba);
+      const int ptype = ch.type;   // (the physical type: INT32 and FLOAT share a layout, DELTA_BINARY_PACKED is for integers)
       uint64_t pos = 0, got = 0, dict_pos = 0, dict_ent = 0;
       uint32_t dict_size = 0, dict_n = 0;
       bool have_dict = false, seen_data = false;
       for (int64_t pageno = 0; got < (uint64_t)g.num_rows; ++pageno) {
         if (pos >= cbytes) needs_host(QH_PQ_R_NUM_VALUES, G, C, pageno);
         PageHeader h;
-        try { h = read_page_header(chunk + pos, cbytes - pos); } catch (const PqNeedsHost& e) { needs_host(e.reason, G, C, pageno); }
+        try { h = read_page_header(chunk + pos, cbytes - pos, set2); } catch (const PqNeedsHost& e) { needs_host(e.reason, G, C, pageno); }
         const uint64_t payload = pos + h.header_bytes;
         if (h.compressed < 0 || (!snappy && h.compressed != h.uncompressed) || (uint64_t)h.compressed > cbytes - payload || h.compressed > 0x7FFFFFFF)
           needs_host(QH_PQ_R_CORRUPT, G, C, pageno);
@@ -424,17 +459,41 @@ inline Plan plan_file(const uint8_t* file, uint64_t n, const std::vector<std::st
         qh_pq_page pg;
         memset(&pg, 0, sizeof pg);
         pg.pos = cbuf + payload; pg.col = (uint32_t)k;
-        if (snappy) {
+        // encoding set 2, a data page V2: its levels lie uncompressed in front of the values, which alone are the page's payload
+        // for the codec and for the passes below. `lev`: the level bytes.
+        const bool v2 = set2 && h.type == PAGE_DATA_V2;
+        uint32_t lev = 0;
+        bool unpacked = snappy;
+        if (v2) {
+          if (!h.has_v2 || h.num_values < 0 || h.num_nulls < 0 || h.num_rows < 0 || h.def_bytes < 0 || h.rep_bytes < 0) needs_host(QH_PQ_R_CORRUPT, G, C, pageno);
+          if (h.num_rows != h.num_values) needs_host(QH_PQ_R_V2_ROWS, G, C, pageno);
+          if (h.rep_bytes != 0) needs_host(QH_PQ_R_V2_REPETITION, G, C, pageno);
+          if (!cp.optional && (h.def_bytes != 0 || h.num_nulls != 0)) needs_host(QH_PQ_R_V2_LEVELS, G, C, pageno);
+          if (h.def_bytes > h.compressed || h.uncompressed < 0 || h.def_bytes > h.uncompressed) needs_host(QH_PQ_R_V2_LEVELS, G, C, pageno);
+          if (h.num_nulls > h.num_values) needs_host(QH_PQ_R_V2_NULLS, G, C, pageno);
+          // (a writer may leave a page's values uncompressed in a compressed chunk, as Arrow does where the codec does not help:
+          // they are read where they lie in the upload, as in an uncompressed chunk)
+          if (snappy && !h.is_compressed) {
+            if (h.compressed != h.uncompressed) needs_host(QH_PQ_R_V2_UNCOMPRESSED, G, C, pageno);
+            unpacked = false;
+          }
+          lev = (uint32_t)h.def_bytes;
+          pg.flags = QH_PQ_F_V2; pg.lev_pos = cbuf + payload; pg.lev_size = lev; pg.num_nulls = (uint32_t)(h.num_nulls > 0xFFFFFFFFll ? 0xFFFFFFFFll : h.num_nulls);
+          pg.pos = cbuf + payload + lev;
+          size -= lev;
+          if (snappy && h.compressed == (int64_t)lev && h.uncompressed == (int64_t)lev) unpacked = false;   // (an empty values part: nothing to unpack)
+        }
+        if (unpacked) {
           // the page is unpacked into a slot of the unpack area first: pos is relative to that area until the upload's size is
           // final (below). The sizes are the file's claims: nothing is reserved for a claim the stream cannot keep.
-          if (h.type == PAGE_DATA_V2) needs_host(QH_PQ_R_PAGE_V2, G, C, pageno);   // (its levels lie outside the compressed part)
+          if (h.type == PAGE_DATA_V2 && !v2) needs_host(QH_PQ_R_PAGE_V2, G, C, pageno);   // (its levels lie outside the compressed part)
           if (h.uncompressed < 0 || h.uncompressed > 0x7FFFFFFF) needs_host(QH_PQ_R_CORRUPT, G, C, pageno);
           qh_pq_unpack u;
           memset(&u, 0, sizeof u);
-          const int bad = qh_snap_check_sizes(chunk + payload, (uint64_t)h.compressed, (uint64_t)h.uncompressed, &u.start);
+          const int bad = qh_snap_check_sizes(chunk + payload + lev, (uint64_t)h.compressed - lev, (uint64_t)h.uncompressed - lev, &u.start);
           if (bad) needs_host(QH_PQ_R_SNAPPY_BASE + bad, G, C, pageno);
-          u.src = cbuf + payload; u.src_size = (uint32_t)h.compressed;
-          u.dst = plan.unpack_bytes; u.dst_size = (uint32_t)h.uncompressed;
+          u.src = cbuf + payload + lev; u.src_size = (uint32_t)h.compressed - lev;
+          u.dst = plan.unpack_bytes; u.dst_size = (uint32_t)h.uncompressed - lev;
           u.page = (uint32_t)plan.pages.size();
           plan.unpack.push_back(u);
           plan.unpack_bytes += ((uint64_t)u.dst_size + 15) & ~(uint64_t)15;
@@ -454,15 +513,32 @@ inline Plan plan_file(const uint8_t* file, uint64_t n, const std::vector<std::st
           dict_ent = plan.num_rows + cp.dict_entries;
           cp.dict_entries += dict_n;
           pg.enc = QH_PQ_ENC_DICTPAGE; pg.num_values = dict_n; pg.ent = dict_ent;
-        } else if (h.type == PAGE_DATA) {
-          if (!h.has_data || h.num_values < 0) needs_host(QH_PQ_R_CORRUPT, G, C, pageno);
+        } else if (h.type == PAGE_DATA || v2) {
+          if (!v2 && (!h.has_data || h.num_values < 0)) needs_host(QH_PQ_R_CORRUPT, G, C, pageno);
           if ((uint64_t)h.num_values > (uint64_t)g.num_rows - got) needs_host(QH_PQ_R_NUM_VALUES, G, C, pageno);
           if (h.encoding == ENC_PLAIN) pg.enc = QH_PQ_ENC_PLAIN;
           else if ((h.encoding == ENC_RLE_DICTIONARY || h.encoding == ENC_PLAIN_DICTIONARY) && !cp.boolean) {
             if (!have_dict) needs_host(QH_PQ_R_CORRUPT, G, C, pageno);
             pg.enc = QH_PQ_ENC_DICT;
-          } else needs_host(QH_PQ_R_ENCODING, G, C, pageno);
-          if (cp.optional && h.def_encoding != ENC_RLE) needs_host(h.def_encoding == ENC_BIT_PACKED ? QH_PQ_R_LEVEL_ENCODING : QH_PQ_R_CORRUPT, G, C, pageno);
+          } else if (set2 && h.encoding == ENC_RLE && cp.boolean) pg.enc = QH_PQ_ENC_RLE_BOOL;
+          else if (set2 && h.encoding == ENC_BYTE_STREAM_SPLIT && pw) pg.enc = QH_PQ_ENC_BSS;
+          else if (set2 && h.encoding == ENC_DELTA_BINARY_PACKED && (ptype == PT_INT32 || ptype == PT_INT64)) pg.enc = QH_PQ_ENC_DELTA;
+          else if (set2 && h.encoding == ENC_DELTA_LENGTH_BYTE_ARRAY && cp.utf8) pg.enc = QH_PQ_ENC_DELTA_LEN;
+          else needs_host(QH_PQ_R_ENCODING, G, C, pageno);
+          if (pg.enc >= QH_PQ_ENC_RLE_BOOL) plan.has_ext = true;
+          if (pg.enc == QH_PQ_ENC_DELTA || pg.enc == QH_PQ_ENC_DELTA_LEN) {
+            qh_pq_dstream d;
+            memset(&d, 0, sizeof d);
+            d.page = (uint32_t)plan.pages.size();
+            d.width = pg.enc == QH_PQ_ENC_DELTA ? pw : (4u | QH_PQ_DS_LENGTHS);
+            if (pg.enc == QH_PQ_ENC_DELTA) {
+              // (the slot is sized by the page's claim, which the row group's rows bound, as they bound the output columns)
+              d.dst = plan.decoded_bytes;
+              plan.decoded_bytes += ((uint64_t)h.num_values * pw + 15) & ~(uint64_t)15;
+            }
+            plan.delta.push_back(d);
+          }
+          if (!v2 && cp.optional && h.def_encoding != ENC_RLE) needs_host(h.def_encoding == ENC_BIT_PACKED ? QH_PQ_R_LEVEL_ENCODING : QH_PQ_R_CORRUPT, G, C, pageno);
           seen_data = true;
           pg.num_values = (uint32_t)h.num_values; pg.first_row = first_row + got;
           pg.dict_pos = dict_pos; pg.dict_size = dict_size; pg.dict_n = dict_n;
@@ -472,7 +548,7 @@ inline Plan plan_file(const uint8_t* file, uint64_t n, const std::vector<std::st
         else if (h.type == PAGE_INDEX) needs_host(QH_PQ_R_INDEX_PAGE, G, C, pageno);
         else needs_host(QH_PQ_R_PAGE_ORDER, G, C, pageno);
         plan.pages.push_back(pg);
-        in_unpack.push_back(snappy ? (uint8_t)(1 | (h.type == PAGE_DATA && have_dict ? 2 : 0)) : (uint8_t)0);
+        in_unpack.push_back(snappy ? (uint8_t)((unpacked ? 1 : 0) | ((h.type == PAGE_DATA || v2) && have_dict ? 2 : 0)) : (uint8_t)0);
         plan.where.push_back(PageWhere{G, C, pageno});
         if (plan.pages.size() >= (1u << 24)) needs_host(QH_PQ_R_CORRUPT, G, C, pageno);   // (the device's error word keeps 8 bits for the reason)
         pos = payload + (uint64_t)h.compressed;
@@ -488,6 +564,12 @@ inline Plan plan_file(const uint8_t* file, uint64_t n, const std::vector<std::st
       if (in_unpack[p] & 1) plan.pages[p].pos += plan.unpack_base;
       if (in_unpack[p] & 2) plan.pages[p].dict_pos += plan.unpack_base;
     }
+  }
+  // ---- ... and the decoded area behind that: a DELTA_BINARY_PACKED page's dict_pos is its slot
+  if (plan.decoded_bytes) {
+    plan.decoded_base = (plan.packed_bytes() + 15) & ~(uint64_t)15;
+    for (qh_pq_dstream& d : plan.delta)
+      if (!(d.width & QH_PQ_DS_LENGTHS)) { d.dst += plan.decoded_base; plan.pages[d.page].dict_pos = d.dst; }
   }
   return plan;
 }

@@ -178,6 +178,10 @@ def read_parquet(path: str, columns: Optional[Sequence[str]] = None, batch_rows:
     format level (`Context.set_parquet_format` / QHIP_PARQUET_FORMAT). Level 1, the default: UNCOMPRESSED chunks — write with
     `compression="NONE"`; pyarrow's default, Snappy, takes the host path — data pages V1, PLAIN and dictionary encodings, flat
     columns. Level 2 also decodes SNAPPY chunks, unpacked on the device; zstd, gzip, lz4 and brotli still take the host path.
+    Which page kinds and encodings are decoded is a second, independent switch, the encoding set
+    (`Context.set_parquet_encodings` / QHIP_PARQUET_ENCODINGS). Set 1, the default: data pages V1 with PLAIN or dictionary
+    values. Set 2 also decodes data pages V2 (`data_page_version="2.0"`), RLE Boolean values, BYTE_STREAM_SPLIT,
+    DELTA_BINARY_PACKED and DELTA_LENGTH_BYTE_ARRAY; DELTA_BYTE_ARRAY still takes the host path.
     Every other file falls back silently to the host read below, which also produces every error message."""
     import os
     import pyarrow.parquet as pq

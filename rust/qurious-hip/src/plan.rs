@@ -80,6 +80,9 @@ impl HipContext {
         // Parquet files as writers produce them by default: Snappy pages are unpacked on the device instead of sending the
         // whole file to the host reader (datasource/file/parquet.rs)
         unsafe { qhip_ctx_set_parquet_format(raw, 2) };
+        // Parquet files as version-2 writers produce them: data pages V2, RLE Booleans, BYTE_STREAM_SPLIT and the DELTA
+        // encodings are decoded on the device too (an independent switch: which codecs is the format level's business)
+        unsafe { qhip_ctx_set_parquet_encodings(raw, 2) };
         Ok(Arc::new(Self { raw, lock: Mutex::new(()), tables: Mutex::new(HashMap::new()) }))
     }
     pub fn raw(&self) -> *mut qhip_ctx {

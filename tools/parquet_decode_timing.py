@@ -18,8 +18,13 @@ without which such a file takes the host path. (d) then also has the unpack pass
 k_pq_levels) with the GB/s of uncompressed bytes it produces, and the header line says how many bytes the projected chunks have
 compressed and uncompressed; (c) copies the compressed bytes, which are what crosses PCIe.
 
+--page-version 2.0 writes data pages V2 and --encoding plain|delta|bss writes without dictionaries, with PLAIN values, with
+DELTA_BINARY_PACKED integers and dates and DELTA_LENGTH_BYTE_ARRAY strings, or with BYTE_STREAM_SPLIT numbers; either sets
+encoding set 2 (Context.set_parquet_encodings). (d) then also has the delta pass (k_pq_delta, between k_pq_levels and
+k_pq_strings); the time of k_pq_values includes k_pq_values_ext, which runs right behind it.
+
     python tools/parquet_decode_timing.py [--gb 1.0] [--runs 10] [--warmup 2] [--repeat 2] [--threads 16] [--columns l_quantity,l_shipdate]
-                                          [--compression none|snappy]
+                                          [--compression none|snappy] [--page-version 1.0|2.0] [--encoding plain|delta|bss]
 """
 import argparse
 import ctypes as C
@@ -43,21 +48,35 @@ from qurious_amd._ffi import DeviceTable  # noqa: E402
 PASSES = ["upload", "k_pq_levels", "k_pq_strings", "k_pq_values", "Utf8 offsets + k_csv_copy_utf8"]
 
 
-def write_file(path, target_bytes, compression="none"):
+def writer_options(schema, page_version, encoding):
+    kw = {"data_page_version": page_version}
+    if encoding:
+        kw["use_dictionary"] = False
+    if encoding == "delta":
+        kw["column_encoding"] = {f.name: "DELTA_LENGTH_BYTE_ARRAY" if pa.types.is_string(f.type) else "DELTA_BINARY_PACKED" for f in schema
+                                 if pa.types.is_string(f.type) or pa.types.is_integer(f.type) or pa.types.is_date32(f.type)}
+    if encoding == "bss":
+        kw["column_encoding"] = {f.name: "BYTE_STREAM_SPLIT" for f in schema
+                                 if pa.types.is_integer(f.type) or pa.types.is_floating(f.type) or pa.types.is_decimal(f.type) or pa.types.is_date32(f.type)}
+    return kw
+
+
+def write_file(path, target_bytes, compression="none", page_version="1.0", encoding=None):
     """lineitem rows, one row group per 2^20 of them, until the file has about target_bytes; returns the row count.
     compression="snappy": the rows the uncompressed file would have, written with pyarrow's defaults"""
     step, rows = 1 << 20, 0
     schema = pa.schema([pa.field(f.name, f.type) for f in synth.LINEITEM_SCHEMA])
     group = lambda first: pa.Table.from_batches([synth.lineitem_batch(first, step)]).cast(schema)   # noqa: E731
+    kw = writer_options(schema, page_version, encoding)
     if compression == "snappy":
         pq.write_table(group(0), path + ".one", compression="NONE", row_group_size=step)
         groups = -(-target_bytes // os.path.getsize(path + ".one"))
         os.remove(path + ".one")
-        with pq.ParquetWriter(path, schema) as w:
+        with pq.ParquetWriter(path, schema, **kw) as w:
             for g in range(groups):
                 w.write_table(group(g * step), row_group_size=step)
         return groups * step
-    with pq.ParquetWriter(path, schema, compression="NONE") as w:
+    with pq.ParquetWriter(path, schema, compression="NONE", **kw) as w:
         while True:
             w.write_table(group(rows), row_group_size=step)
             rows += step
@@ -85,25 +104,30 @@ def main():
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--columns", type=str, default="", help="comma-separated projection (default: every column)")
     ap.add_argument("--compression", choices=["none", "snappy"], default="none", help="snappy: pyarrow's defaults, decoded at format level 2")
+    ap.add_argument("--page-version", choices=["1.0", "2.0"], default="1.0", help="2.0: data pages V2, decoded at encoding set 2")
+    ap.add_argument("--encoding", choices=["plain", "delta", "bss"], default=None, help="no dictionaries; delta and bss are decoded at encoding set 2")
     args = ap.parse_args()
     pa.set_cpu_count(args.threads)
     columns = [c for c in args.columns.split(",") if c] or None
     ctx = q.get_context()
     if args.compression == "snappy":
         ctx.set_parquet_format(2)
+    if args.page_version == "2.0" or args.encoding in ("delta", "bss"):
+        ctx.set_parquet_encodings(2)
     hip = C.CDLL(None)   # (libqhip.so is loaded globally and brings the HIP runtime with it)
     hip.hipMalloc.argtypes, hip.hipMemcpy.argtypes, hip.hipFree.argtypes = [C.POINTER(C.c_void_p), C.c_size_t], [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int], [C.c_void_p]
     with tempfile.TemporaryDirectory() as d:
         path = os.path.join(d, "lineitem.parquet")
-        rows = write_file(path, int(args.gb * 1e9), args.compression)
+        rows = write_file(path, int(args.gb * 1e9), args.compression, args.page_version, args.encoding)
         nbytes = os.path.getsize(path)
         md = pq.ParquetFile(path).metadata
         names = md.schema.names
         want = set(columns) if columns else set(names)
         chunk_bytes = sum(md.row_group(g).column(c).total_compressed_size for g in range(md.num_row_groups) for c in range(md.num_columns) if names[c] in want)
         plain_bytes = sum(md.row_group(g).column(c).total_uncompressed_size for g in range(md.num_row_groups) for c in range(md.num_columns) if names[c] in want)
+        values = args.encoding or "writer's default"
         print(f"device {ctx.device_name()}; {path}: {nbytes} bytes, {rows} rows in {md.num_row_groups} row groups, columns {sorted(want)}: {chunk_bytes} bytes of "
-              f"projected chunks ({args.compression}; {plain_bytes} bytes uncompressed); median (min) of {args.runs} calls after {args.warmup} warm-up calls; host read with {args.threads} threads", flush=True)
+              f"projected chunks ({args.compression}, pages V{args.page_version[0]}, {values} values; {plain_bytes} bytes uncompressed); median (min) of {args.runs} calls after {args.warmup} warm-up calls; host read with {args.threads} threads", flush=True)
 
         def host_path():
             t = datasource.read_parquet(path, columns, device=False)
@@ -135,7 +159,7 @@ def main():
         per = []
         for _ in range(args.warmup + args.runs):
             device_path()
-            per.append(ctx.parquet_pass_ms() + [ctx.parquet_unpack_ms()])
+            per.append(ctx.parquet_pass_ms() + [ctx.parquet_unpack_ms(), ctx.parquet_delta_ms()])
         ctx.set_timing(False)
         per = per[args.warmup:]
         kernels = 0.0
@@ -147,6 +171,10 @@ def main():
                 med = statistics.median(p[5] for p in per)
                 kernels += med
                 print(f"(d) {'k_pq_unsnap (unpack)':32s} {med:9.3f} ms  {plain_bytes / max(med, 1e-6) / 1e6:9.1f} GB/s of uncompressed bytes", flush=True)
+            if k == 1 and args.encoding == "delta":
+                med = statistics.median(p[6] for p in per)
+                kernels += med
+                print(f"(d) {'k_pq_delta':32s} {med:9.3f} ms  {chunk_bytes / max(med, 1e-6) / 1e6:9.1f} GB/s of chunk bytes", flush=True)
         print(f"(d) kernels together (all but the upload) {kernels:9.3f} ms  {chunk_bytes / max(kernels, 1e-6) / 1e6:9.1f} GB/s of chunk bytes", flush=True)
         del src
         m.close()
