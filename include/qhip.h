@@ -538,6 +538,17 @@ int qhip_table_column_ascending(qhip_ctx* ctx, const qhip_table* t, int64_t col,
 /* Sorted dense join builds launched on this context, and how many of them found their keys out of order (or too wide a gap)
  * and ran again with the atomic build. */
 int qhip_ctx_sorted_build_counts(qhip_ctx* ctx, int64_t* launched, int64_t* fallbacks);
+/* Hash join probes on this context whose pass 2 summed the per-chunk pair counters itself (joins of deferred size with few
+ * enough chunks: no scan launch), and those whose counters were scanned in a launch of their own (QHIP_JOIN_FOLD_SCAN). */
+int qhip_ctx_join_scan_counts(qhip_ctx* ctx, int64_t* folded, int64_t* launched);
+/* Index vectors that are owed like the columns behind them (QHIP_JOIN_LAZY_INDEX): out[0] = hash joins on this context that left
+ * their build-side index vector as dense key indices, out[1] = such vectors translated to build rows after all (a reader came),
+ * out[2] = index compositions inner[outer] made at a first read, out[3] = owed join key columns written after all. */
+int qhip_ctx_lazy_index_counts(qhip_ctx* ctx, int64_t* out /* 4 values */);
+/* What a column still owes, without launching anything: 0 = nothing (a plain column, or a gather that has been made), 1 = a
+ * deferred gather whose index vector is ready, 2 = ... whose index vector awaits its translation from dense key indices, 3 = ... whose
+ * index vector awaits its composition, 4 = a dense join's key column that has not been written. */
+int qhip_table_column_index_state(const qhip_table* t, int64_t col, int32_t* out);
 /* Concatenate tables with identical schemas (batches appended in order). */
 int qhip_table_concat(qhip_ctx* ctx, const qhip_table* const* tables, int32_t n, qhip_table** out);
 

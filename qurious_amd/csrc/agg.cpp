@@ -120,7 +120,7 @@ void fill_kargs(Ctx* ctx, const qhip_table* t, const KernelBindings& b, HKArgs& 
     if (s < b.indirect.size() && b.indirect[s]) {   // read through the deferred gather's index vector (InputCol::indirect)
       if (!indirect_eligible(c0)) fail(QHIP_HIP_ERROR, "a column planned as an indirect read has been gathered meanwhile (internal error)");
       a.c[s].v = c0.deferred->src.values->ptr;
-      a.c[s].d = (const uint8_t*)c0.deferred->idx->ptr;
+      a.c[s].d = (const uint8_t*)index_rows(ctx, c0.deferred->idx);   // (looked up / composed now if it was owed)
       if (s < b.rec.size() && b.rec[s]) {   // ... as a field of the source's record copy (ColRange::rec_buf)
         const DevColumn& src = c0.deferred->src;
         const ColRange& sh = *src.range;

@@ -169,9 +169,35 @@ struct DeferredUpload {
   bool done = false;
   DevColumn result;
 };
+// An index vector that is OWED like the columns read through it: one object per group of columns that share a vector. The
+// first reader resolves it (index_rows, relops.cpp), once, for every column and every table that shares it.
+//  * ready:               `rows` holds the u32 row numbers.
+//  * pending translation: `keys` holds dense key indices (key - min: what the dense probe's entries are) and the build row of
+//                         each is looked up on first read (qh_dense_build_row) — `table` keeps the join's row_of / rank + bitmap
+//                         alive for that. A join whose build-side columns nobody reads never pays the lookup (Q3's join 1).
+//  * pending composition: rows = inner[outer], either of them possibly pending itself. A parent join composes only the groups
+//                         that somebody reads.
+struct LazyIndex {
+  std::shared_ptr<DevBuf> rows;   // ready: u32 row numbers (m + 1 of them allocated); kNullIdx -> NULL
+  uint64_t m = 0;
+  std::shared_ptr<LazyIndex> keys;                    // pending translation of this (ready) vector of key indices ...
+  std::shared_ptr<DevBuf> table;                      // ... through the dense table it keeps alive:
+  const uint32_t *row_of = nullptr, *rank = nullptr, *rank_bits = nullptr;   // row_of form, or rank + bitmap (pointers into `table`)
+  uint32_t build_last = 0;
+  std::shared_ptr<LazyIndex> inner, outer;            // pending composition
+  bool ready() const { return (bool)rows; }
+  static std::shared_ptr<LazyIndex> of(const std::shared_ptr<DevBuf>& rows, uint64_t m) {
+    auto x = std::make_shared<LazyIndex>();
+    x->rows = rows; x->m = m;
+    return x;
+  }
+};
 struct DeferredGather {
   DevColumn src;                  // never itself deferred (index vectors are composed instead)
-  std::shared_ptr<DevBuf> idx;    // u32 row numbers into src; kNullIdx -> NULL when idx_may_be_null
+  std::shared_ptr<LazyIndex> idx; // u32 row numbers into src, possibly owed; kNullIdx -> NULL when idx_may_be_null
+  // ... or the join key of a dense join whose build-side index vector is pending: value[k] = key_min + key_of[k] (key_of: a vector
+  // of dense key indices), written as a plain Int64 column when somebody reads it. src carries the type only and idx is empty.
+  std::shared_ptr<LazyIndex> key_of; int64_t key_min = 0;
   uint64_t m = 0;
   bool idx_may_be_null = false;
   bool idx_ascends = false;       // idx is strictly ascending (an Inner join's probe side with unique build keys, a selection)
@@ -260,6 +286,9 @@ struct Ctx {
   std::unordered_set<uint64_t> join_dup_builds;   // build sides (key policy x row count) seen with duplicate keys: no speculation
   std::unordered_set<uint64_t> join_unsorted_builds;   // ... seen out of order by the sorted dense build: the atomic build
   int64_t sorted_builds = 0, sorted_build_fallbacks = 0;   // sorted dense builds launched / found out of order (qhip_ctx_sorted_build_counts)
+  int64_t lazy_index_joins = 0;   // joins that left their build-side index vector owed
+  int64_t index_translations = 0, index_compositions = 0, lazy_key_columns = 0;   // owed index vectors / join key columns made after all (qhip_ctx_lazy_index_counts)
+  int64_t join_scans_folded = 0, join_scans_launched = 0;  // chunk counters summed by pass 2 itself / scanned in a launch of their own (qhip_ctx_join_scan_counts)
   // Deferred sizing. A hash join remembers how many pairs it produced (keyed by its expressions, type and probe rows, NOT
   // by the data). The next time the same join runs under a consumer that can read a device-side row count
   // (allow_deferred_sizes > 0: HashAggregate's input, a hash join's build side) it does not wait for its pair total: the

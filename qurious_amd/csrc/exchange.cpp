@@ -283,7 +283,7 @@ void partition_scatter(Ctx* ctx, const qhip_table* in, const int32_t* keep, int 
     const int width = dtype_width(c0.type);
     if (indirect_eligible(c0)) {
       auto out = std::make_shared<DevBuf>((size_t)total * (size_t)width);
-      push(c0.deferred->src.values->ptr, c0.deferred->idx->as<uint32_t>(), out->ptr, width);
+      push(c0.deferred->src.values->ptr, index_rows(ctx, c0.deferred->idx), out->ptr, width);
       moved.push_back(Moved{c, out, width});
       continue;
     }
@@ -1147,6 +1147,28 @@ int qhip_ctx_sorted_build_counts(qhip_ctx* ctx, int64_t* launched, int64_t* fall
   if (!ctx || !launched || !fallbacks) return QHIP_INVALID_ARGUMENT;
   *launched = ctx->sorted_builds;
   *fallbacks = ctx->sorted_build_fallbacks;
+  return QHIP_OK;
+}
+
+int qhip_ctx_join_scan_counts(qhip_ctx* ctx, int64_t* folded, int64_t* launched) {
+  if (!ctx || !folded || !launched) return QHIP_INVALID_ARGUMENT;
+  *folded = ctx->join_scans_folded;
+  *launched = ctx->join_scans_launched;
+  return QHIP_OK;
+}
+
+int qhip_ctx_lazy_index_counts(qhip_ctx* ctx, int64_t* out) {
+  if (!ctx || !out) return QHIP_INVALID_ARGUMENT;
+  out[0] = ctx->lazy_index_joins;
+  out[1] = ctx->index_translations;
+  out[2] = ctx->index_compositions;
+  out[3] = ctx->lazy_key_columns;
+  return QHIP_OK;
+}
+
+int qhip_table_column_index_state(const qhip_table* t, int64_t col, int32_t* out) {
+  if (!t || !out || col < 0 || col >= (int64_t)t->cols.size()) return QHIP_INVALID_ARGUMENT;
+  *out = index_state(t->cols[(size_t)col]);
   return QHIP_OK;
 }
 

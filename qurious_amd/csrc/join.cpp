@@ -95,6 +95,9 @@ struct JoinTuning {
   int wide_keys;              // QHIP_JOIN_WIDE_KEYS 0 never / 1 when the packed key does not fit / 2 every hash join over plain key columns:
                               // keys of both sides encoded to shared key codes first (policy, off; 2 = tests) — the context's own mode goes first
   int wide_key_hash_bits;     // QHIP_JOIN_WIDE_KEY_HASH_BITS (1..63): only so many bits of the encoding's hash (test forcing: long probe chains)
+  bool lazy_index;            // QHIP_JOIN_LAZY_INDEX=0: pass 2 always looks the build rows up and writes the key column (measurement; relops.cpp reads it for the compositions)
+  bool fold_scan;             // QHIP_JOIN_FOLD_SCAN=0: a deferred-size join scans its chunk counters in a launch of its own, as every other join does (measurement)
+  uint64_t fold_max_chunks;   // QHIP_JOIN_FOLD_SCAN_MAX_CHUNKS (0..8192): most chunks pass 2 sums by itself (test forcing: the separate scan above it)
 };
 JoinTuning read_join_tuning() {
   JoinTuning t;
@@ -121,6 +124,9 @@ JoinTuning read_join_tuning() {
   t.eager_offsets = env_int("QHIP_EAGER_OFFSETS", 0) != 0;
   t.wide_keys = env_int("QHIP_JOIN_WIDE_KEYS", 0);
   t.wide_key_hash_bits = env_int("QHIP_JOIN_WIDE_KEY_HASH_BITS", 0);
+  t.lazy_index = env_int("QHIP_JOIN_LAZY_INDEX", 1) != 0;
+  t.fold_scan = env_int("QHIP_JOIN_FOLD_SCAN", 1) != 0;
+  t.fold_max_chunks = (uint64_t)std::max(0, std::min(QH_JOIN_FOLD_MAX_CHUNKS, env_int("QHIP_JOIN_FOLD_SCAN_MAX_CHUNKS", QH_JOIN_FOLD_MAX_CHUNKS)));
   return t;
 }
 
@@ -176,11 +182,15 @@ struct JoinRun {
   DevBuf visited; bool visited_done = false;
   DevBuf ent_slot, ent_row, tile_tot, tile_nent;   // pass 1: (slot, probe row) per matching row; pair total / entries per chunk
   uint64_t nchunks = 0, tiles_per_wave = 0, chunk_rows = 0;
+  bool fold_scan = false;   // tile_tot holds the chunks' pair counts, unscanned: pass 2 (of a deferred-size join) sums them itself
   std::string probe_name;   // (the entry point launched, for the statistics)
   bool probe_timed = false;
   DevBuf cnt, pair_off, b_idx, p_idx;   // pass 2: pairs per probe row and their first position (Right / Full); the pairs
   uint64_t M = 0;
   bool mat_key = false;
+  // the build-side index vector is left as pass 1's dense key indices (key - min) and owed (LazyIndex, pending translation): pass 2
+  // looked nothing up and wrote no key column. Decided before pass 2 (wants_lazy_build), true only if pass 2 took its pairs-only branch
+  bool lazy_build = false;
   std::shared_ptr<DevBuf> key_vals;   // the join key of every output row (mat_key)
   std::shared_ptr<DevBuf> rows_blk; std::shared_ptr<uint64_t> rows_final; const uint32_t* deferred_slot = nullptr;   // deferred size
   DevBuf cnt2, off2, out_off;   // surviving pairs per probe row behind the residual filter, their scan; Right / Full: output positions
@@ -510,6 +520,19 @@ bool materializes_key(const JoinArgs& a, const JoinTuning& t, const JoinCall& c,
          a.R->cols[(size_t)a.rex[a.on_r[0]].column].type.id == QHIP_INT64 && t.key_materialize;
 }
 
+// The build-side index vector may stay owed: the dense layout with unique build keys, an Inner join without residual filter —
+// pass 2's pairs-only branch, whose entries ARE the key indices — and a build side without a pending gather among its columns
+// (a parent's composition would read the vector at once: Q3's join 2 translates in pass 2 as before; its join 1, whose customer
+// columns nobody reads, never translates).
+bool wants_lazy_build(const JoinArgs& a, const JoinTuning& t, const JoinCall& c, const JoinRun& r) {
+  if (!t.lazy_index || t.eager_gather || !c.dense || !r.unique_keys || a.join_type != QHIP_JOIN_INNER || a.froot >= 0 || c.pad_right || c.has_tail ||
+      c.mark_in_probe || r.start_ptr)
+    return false;
+  for (const DevColumn& col : a.L->cols)
+    if (col.deferred && !col.deferred->done) return false;
+  return true;
+}
+
 // ---- probe. Pass 1 (JIT: fused scan filter + key words + lookup straight from the probe table's columns) leaves one
 // (slot, probe row) entry per MATCHING probe row and one pair count per 256-row tile; the tile counts are scanned; pass 2 writes the pairs in
 // probe-row order. LeftSemi / LeftAnti without a residual filter only need the visited bits: pass 1 sets them.
@@ -561,7 +584,11 @@ void launch_probe(Ctx* ctx, const JoinArgs& a, const JoinTuning& t, const JoinCa
   QHIP_HIP_CHECK(hipModuleLaunchKernel(mod->fn, pg.grid, 1, 1, pk.waves_per_wg * 64, 1, 1, (unsigned)pk.dyn_lds, s, args, nullptr));
   time_mark(ctx, 3);
   r.probe_timed = true;
-  if (c.want_pairs) exclusive_scan_u32(r.tile_tot.as<uint32_t>(), r.tile_tot.as<uint32_t>(), r.nchunks, c.dstat + 2 * QS_WORDS, s);
+  // (a join of deferred size needs neither the offsets nor the total before pass 2, and pass 2 can sum a few thousand counters
+  // in every workgroup: the scan's launch — one workgroup, ~5 us of stream time — is dropped there)
+  r.fold_scan = c.defer && c.want_pairs && t.fold_scan && r.nchunks <= t.fold_max_chunks && join_emit_can_fold(r.nchunks, r.tile_tot.as<uint32_t>());
+  if (c.want_pairs && !r.fold_scan) exclusive_scan_u32(r.tile_tot.as<uint32_t>(), r.tile_tot.as<uint32_t>(), r.nchunks, c.dstat + 2 * QS_WORDS, s);
+  if (c.want_pairs) ++(r.fold_scan ? ctx->join_scans_folded : ctx->join_scans_launched);
 }
 
 // pass 2: the pairs of every chunk's entries into b_idx / p_idx (room for r.M pairs). publish != null, the deferred form: it also
@@ -576,14 +603,16 @@ void emit_pairs(Ctx* ctx, const JoinCall& c, JoinRun& r, uint32_t* publish) {
     QHIP_HIP_CHECK(hipMemsetAsync(r.cnt.ptr, 0, r.cnt.bytes, ctx->stream));   // pass 2 only visits matching probe rows
   }
   if (deferred) r.rows_blk = std::make_shared<DevBuf>(64);   // the output table's device-side row count
-  if (r.mat_key) r.key_vals = std::make_shared<DevBuf>((r.M + 1) * 8);
-  const uint32_t* const dense_table = (const uint32_t*)r.table;
+  if (r.mat_key && !r.lazy_build) r.key_vals = std::make_shared<DevBuf>((r.M + 1) * 8);
+  // (owed build rows: without row_of / rank pass 2 stores the entries — the key indices — as they are)
+  const uint32_t* const dense_table = r.lazy_build ? nullptr : (const uint32_t*)r.table;
   launch_join_emit(r.ent_slot.as<uint32_t>(), r.ent_row.as<uint32_t>(), r.tile_nent.as<uint32_t>(), r.tile_tot.as<uint32_t>(), r.count, r.start_ptr,
                    r.rows_ptr, c.dense && !c.dense_rank ? dense_table : nullptr, r.nchunks, r.chunk_rows, r.b_idx.as<uint32_t>(), r.p_idx.as<uint32_t>(),
                    c.pad_right && !deferred ? r.pair_off.as<uint32_t>() : nullptr, c.pad_right && !deferred ? r.cnt.as<uint32_t>() : nullptr,
                    c.mark_in_probe && !deferred ? r.visited.as<uint32_t>() : nullptr, deferred ? (uint32_t)r.M : 0xFFFFFFFFu, deferred ? c.dstat : nullptr,
                    publish, deferred ? r.rows_blk->as<uint32_t>() : nullptr, ctx->stream, r.key_vals ? r.key_vals->as<int64_t>() : nullptr, (uint64_t)c.kmin,
-                   c.dense_rank ? dense_table : nullptr, (const uint32_t*)r.bloom, c.dense ? (uint32_t)(c.B - 1) : 0xFFFFFFFFu);
+                   c.dense_rank ? dense_table : nullptr, (const uint32_t*)r.bloom, c.dense ? (uint32_t)(c.B - 1) : 0xFFFFFFFFu, deferred && r.fold_scan);
+  if (r.lazy_build) ++ctx->lazy_index_joins;
 }
 
 // deferred size: no read-back — the status block + total go to a page-locked slot that the consumer's synchronisation checks
@@ -733,7 +762,7 @@ void concat_index_vectors(Ctx* ctx, JoinRun& r) {
 
 // ---- output columns (build_batch_from_indices, utils/batch.rs:18-61): the reference gathers every column of both
 // sides; here the gathers are deferred until a column is read (a parent join / aggregate touches only a few)
-void make_output_columns(Ctx* ctx, const JoinArgs& a, const JoinTuning& t, const JoinCall& c, const JoinRun& r, qhip_table* out) {
+void make_output_columns(Ctx* ctx, const JoinArgs& a, const JoinTuning& t, const JoinCall& c, JoinRun& r, qhip_table* out) {
   const qhip_table *L = a.L, *R = a.R;
   const uint64_t total_rows = r.total_rows;
   out->ctx = ctx;
@@ -750,8 +779,48 @@ void make_output_columns(Ctx* ctx, const JoinArgs& a, const JoinTuning& t, const
       out->nullable.push_back(src->nullable[k] || side_nullable);
     }
   };
-  add_side(L, r.b_all, left_nullable, false);
+  // owed build rows: b_all holds key indices. The object every build-side column shares keeps the dense table (row_of, or rank +
+  // bitmap: the arena, which would otherwise go back to the pool with this call) until the first reader looks the rows up
+  std::shared_ptr<LazyIndex> key_idx;
+  if (r.lazy_build) {   // (an Inner join: no tail rows, b_all is pass 2's vector)
+    key_idx = LazyIndex::of(r.b_all, total_rows);
+    auto owed = std::make_shared<LazyIndex>();
+    owed->m = total_rows;
+    owed->keys = key_idx;
+    owed->table = std::make_shared<DevBuf>(std::move(r.arena));
+    (c.dense_rank ? owed->rank : owed->row_of) = (const uint32_t*)r.table;
+    owed->rank_bits = c.dense_rank ? (const uint32_t*)r.bloom : nullptr;
+    owed->build_last = (uint32_t)(c.B - 1);
+    defer_gather(ctx, L->cols, owed, total_rows, left_nullable, out->cols, false);
+    for (size_t k = 0; k < L->cols.size(); ++k) {
+      out->names.push_back(L->names[k]);
+      out->nullable.push_back(L->nullable[k] || left_nullable);
+    }
+  } else {
+    add_side(L, r.b_all, left_nullable, false);
+  }
   if (!c.semi_anti) add_side(R, r.p_all, right_nullable, probe_idx_ascends);
+  if (key_idx && r.mat_key) {
+    // ... and the key columns are owed with them: key_min + key index, written as plain columns when somebody reads them
+    auto owed_key = [&](const DevColumn& src) {
+      DevColumn col;
+      col.type = src.type;
+      col.length = (int64_t)total_rows;
+      col.value_maxabs = src.value_maxabs;
+      col.range = src.range;             // (a subset of the source's values: its bounds hold)
+      col.range_inherited = true;
+      auto d = std::make_shared<DeferredGather>();
+      d->src.type = src.type; d->src.value_maxabs = src.value_maxabs; d->src.range = src.range; d->src.range_inherited = true;
+      d->key_of = key_idx; d->key_min = c.kmin; d->m = total_rows;
+      col.deferred = d;
+      return col;
+    };
+    const qhip_expr& lk = a.lex[a.on_l[0]];
+    const size_t rc = (size_t)a.rex[a.on_r[0]].column;
+    out->cols[L->cols.size() + rc] = owed_key(R->cols[rc]);
+    if (lk.kind == QHIP_EXPR_COLUMN && lk.column >= 0 && lk.column < (int)L->cols.size() && L->cols[(size_t)lk.column].type.id == QHIP_INT64)
+      out->cols[(size_t)lk.column] = owed_key(L->cols[(size_t)lk.column]);
+  }
   if (r.key_vals) {
     auto plain = [&](const DevColumn& src) {
       DevColumn col;
@@ -888,6 +957,7 @@ qhip_table* hash_join(Ctx* ctx, const JoinArgs& a, const JoinTuning* first = nul
     r.ent_row.alloc((c.P + 1) * 4);
     r.probe_name = c.dense ? "qk_join_probe_dense" : "qk_join_probe";
     r.mat_key = materializes_key(a, t, c, r);
+    r.lazy_build = c.P > 0 && wants_lazy_build(a, t, c, r);   // (without probe rows there is no pass 2 and nothing to owe)
     if (c.P > 0) {
       launch_probe(ctx, a, t, c, r);
       if (c.defer) emit_deferred(ctx, c, r);

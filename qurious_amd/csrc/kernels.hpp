@@ -67,13 +67,22 @@ constexpr int kGatherBatch = 8;
 struct GatherBatch { GatherDesc d[kGatherBatch]; };
 void launch_gather_multi(const GatherBatch& b, int n, hipStream_t s);
 void launch_gather_u32_nullable(const uint32_t* inner, const uint32_t* idx, uint32_t* out, uint64_t m, hipStream_t s);
+// rows[k] = the build row of dense key index keys[k] (row_of form, or rank + bitmap) when rows is set; key_out[k] = key_min + keys[k] when set
+void launch_dense_translate(const uint32_t* keys, uint32_t* rows, uint64_t m, const uint32_t* row_of, const uint32_t* rank, const uint32_t* rank_bits,
+                            uint32_t build_last, int64_t* key_out, uint64_t key_min, hipStream_t s);
 void launch_lower_bound_u32(const uint32_t* a, uint64_t m, const uint32_t* m_dev, const uint64_t* bound, uint32_t nb, uint32_t* pos, hipStream_t s);
 void launch_bytes_to_bits(const uint8_t* bytes, uint32_t gen, uint32_t* bits, uint32_t nwords, uint32_t* counters, uint32_t* status, hipStream_t s);
+// fold_scan (a join of deferred size only: stat_block set): chunk_off holds the per-chunk pair COUNTS and pass 2 sums them itself —
+// no scan launch in front of it. join_emit_can_fold says whether it can: few enough chunks, counters aligned for 16-byte loads.
+#define QH_JOIN_FOLD_MAX_CHUNKS 8192
+inline bool join_emit_can_fold(uint64_t nchunks, const uint32_t* chunk_counts) {
+  return nchunks > 0 && nchunks <= QH_JOIN_FOLD_MAX_CHUNKS && ((uintptr_t)chunk_counts & 15u) == 0;
+}
 void launch_join_emit(const uint32_t* ent_slot, const uint32_t* ent_row, const uint32_t* chunk_nent, const uint32_t* chunk_off, const uint32_t* count,
                       const uint32_t* start, const uint32_t* rows, const uint32_t* row_of, uint64_t nchunks, uint64_t chunk_rows, uint32_t* b_idx, uint32_t* p_idx,
                       uint32_t* pair_off, uint32_t* cnt_out, uint32_t* visited, uint32_t cap, const uint32_t* stat_block, uint32_t* publish,
                       uint32_t* rows_out, hipStream_t s, int64_t* key_out = nullptr, uint64_t key_min = 0, const uint32_t* rank = nullptr,
-                      const uint32_t* rank_bits = nullptr, uint32_t build_last = 0xFFFFFFFFu);
+                      const uint32_t* rank_bits = nullptr, uint32_t build_last = 0xFFFFFFFFu, bool fold_scan = false);
 void launch_join_mark(const uint32_t* b_idx, const uint32_t* p_idx, uint64_t m, uint32_t* visited_bits, uint32_t* cnt_per_probe, hipStream_t s);
 void launch_join_out_counts(const uint32_t* cnt, uint64_t np, uint32_t* out_cnt, hipStream_t s);
 void launch_join_adjust_right(const uint32_t* b_in, const uint32_t* cnt, const uint32_t* in_off, const uint32_t* out_off, uint64_t np,

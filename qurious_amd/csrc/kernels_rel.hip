@@ -631,16 +631,58 @@ __global__ __launch_bounds__(QH_BLOCK) void k_join_emit(const u32* ent_slot, con
                                                        const u32* count, const u32* start, const u32* rows, const u32* row_of, u64 nchunks, u64 chunk_rows, u32* b_idx,
                                                        u32* p_idx, u32* pair_off, u32* cnt_out, u32* visited, u32 cap, const u32* stat_block,
                                                        u32* publish, u32* rows_out, i64* key_out, u64 key_min, const u32* rank, const u32* rank_bits,
-                                                       u32 build_last) {
+                                                       u32 build_last, u32 fold) {
+  // fold != 0 (a join of deferred size, nchunks <= QH_JOIN_FOLD_MAX_CHUNKS, the grid covers every chunk in one trip): chunk_off
+  // holds pass 1's per-chunk pair COUNTS, not their scan, and there was no scan launch. Every workgroup loads all the counters
+  // (16 bytes per load, every load issued before the first sum: 16-32 KB out of L2) and one block reduction gives the sum below
+  // its first chunk and the grand total; a wavefront adds the counts of the workgroup's chunks in front of its own. Nothing waits
+  // on another workgroup and there is no atomic.
+  u32 fold_below = 0, fold_total = 0;
+  if (fold) {
+    static_assert((QH_BLOCK / 64) % 4 == 0, "a workgroup's first chunk must start a 16-byte vector of counters");
+    typedef u32 v4u __attribute__((ext_vector_type(4)));
+    constexpr int MAXV = QH_JOIN_FOLD_MAX_CHUNKS / 4 / QH_BLOCK;
+    __shared__ u32 fold_s[2][QH_BLOCK / 64];
+    const u32 n = (u32)nchunks;
+    const u32 c0 = blockIdx.x * (u32)(QH_BLOCK / 64);
+    const u32 wave = threadIdx.x >> 6;
+    u32 front[QH_BLOCK / 64 - 1];
+#pragma unroll
+    for (u32 w = 0; w + 1 < QH_BLOCK / 64; ++w) front[w] = (w < wave && c0 + w < n) ? chunk_off[c0 + w] : 0u;
+    v4u v[MAXV];
+#pragma unroll
+    for (int k = 0; k < MAXV; ++k) {
+      const u32 i = ((u32)k * QH_BLOCK + threadIdx.x) * 4u;
+      v[k] = (v4u)(0u);
+      if (i + 3u < n) v[k] = *(const v4u*)(chunk_off + i);
+      else if (i < n) { v[k].x = chunk_off[i]; v[k].y = i + 1u < n ? chunk_off[i + 1] : 0u; v[k].z = i + 2u < n ? chunk_off[i + 2] : 0u; }
+    }
+    u32 all = 0, below = 0;
+#pragma unroll
+    for (int k = 0; k < MAXV; ++k) {
+      const u32 i = ((u32)k * QH_BLOCK + threadIdx.x) * 4u;
+      const u32 s4 = v[k].x + v[k].y + v[k].z + v[k].w;
+      all += s4;
+      below += i < c0 ? s4 : 0u;   // (c0 is a multiple of 4: a vector lies wholly below it or not at all)
+    }
+    all = (u32)qh_wave_sum_u64((u64)all);
+    below = (u32)qh_wave_sum_u64((u64)below);
+    if (qh_lane() == 0) { fold_s[0][wave] = all; fold_s[1][wave] = below; }
+    __syncthreads();
+#pragma unroll
+    for (u32 w = 0; w < QH_BLOCK / 64; ++w) { fold_total += fold_s[0][w]; fold_below += fold_s[1][w]; }
+#pragma unroll
+    for (u32 w = 0; w + 1 < QH_BLOCK / 64; ++w) fold_below += front[w];
+  }
   // a join of deferred size (cap = the room its output has; stat_block = [build status | probe status | pair total]): rows
   // [total, cap) of the index vectors repeat row 0 of both sides (valid to gather, never counted), the total goes to the
   // output table's device-side row count and the status block to page-locked host memory, where the consumer's
   // synchronisation finds it — all in this launch instead of a fill, a copy and a device-to-device copy behind it
   if (stat_block) {
-    const u32 total = stat_block[2 * QS_WORDS];
+    const u32 total = fold ? fold_total : stat_block[2 * QS_WORDS];
     for (u64 k = (u64)total + (u64)blockIdx.x * QH_BLOCK + threadIdx.x; k < cap; k += (u64)gridDim.x * QH_BLOCK) { b_idx[k] = 0; p_idx[k] = 0; }
     if (blockIdx.x == 0 && threadIdx.x <= 2 * QS_WORDS) {
-      publish[threadIdx.x] = stat_block[threadIdx.x];
+      publish[threadIdx.x] = threadIdx.x == 2 * QS_WORDS ? total : stat_block[threadIdx.x];
       if (threadIdx.x == 2 * QS_WORDS) *rows_out = total;
       __threadfence_system();
     }
@@ -649,7 +691,7 @@ __global__ __launch_bounds__(QH_BLOCK) void k_join_emit(const u32* ent_slot, con
   // a wavefront per chunk (the consecutive tiles one probe wavefront owned): its entries are one run
   for (u64 ch = (u64)blockIdx.x * (QH_BLOCK / 64) + (threadIdx.x >> 6); ch < nchunks; ch += (u64)gridDim.x * (QH_BLOCK / 64)) {
     const u32 n = chunk_nent[ch];
-    u32 base = chunk_off[ch];
+    u32 base = fold ? fold_below : chunk_off[ch];
     const u64 e0 = ch * chunk_rows;
     if (!start && !pair_off && !visited) {
       // unique build keys, nothing but the pairs wanted (every Inner FK -> PK join): entry j of the chunk IS pair base + j, so
@@ -844,6 +886,17 @@ __global__ __launch_bounds__(QH_BLOCK) void k_gather_u32_nullable(const u32* inn
   for (u64 k = (u64)blockIdx.x * QH_BLOCK + threadIdx.x; k < m; k += (u64)gridDim.x * QH_BLOCK) {
     const u32 i = idx[k];
     out[k] = i == QH_NULL_IDX ? QH_NULL_IDX : inner[i];
+  }
+}
+// A dense join's build-side index vector, owed until somebody reads it (LazyIndex, pending translation): the build row of every
+// dense key index (key - min), and — when key_out is set — the join key itself as a plain Int64 column. Rows behind the pair
+// count of a deferred-size join hold index 0: qh_dense_build_row clamps whatever it finds there to a valid row.
+__global__ __launch_bounds__(QH_BLOCK) void k_dense_translate(const u32* keys, u32* rows, u64 m, const u32* row_of, const u32* rank, const u32* rank_bits,
+                                                             u32 build_last, i64* key_out, u64 key_min) {
+  for (u64 k = (u64)blockIdx.x * QH_BLOCK + threadIdx.x; k < m; k += (u64)gridDim.x * QH_BLOCK) {
+    const u32 i = keys[k];
+    if (rows) rows[k] = qh_dense_build_row(row_of, rank, rank_bits, build_last, i);
+    if (key_out) key_out[k] = (i64)(key_min + (u64)i);
   }
 }
 __global__ __launch_bounds__(QH_BLOCK) void k_iota_u32(u32* out, u64 n, u32 first) {
@@ -1323,6 +1376,11 @@ void launch_sort_utf8_chunk(const int32_t* offsets, const uint8_t* data, const u
 void launch_gather_u32_nullable(const uint32_t* inner, const uint32_t* idx, uint32_t* out, uint64_t m, hipStream_t s) {
   if (m) hipLaunchKernelGGL(k_gather_u32_nullable, dim3(grid_for(m)), dim3(QH_BLOCK), 0, s, (const u32*)inner, (const u32*)idx, (u32*)out, (u64)m);
 }
+void launch_dense_translate(const uint32_t* keys, uint32_t* rows, uint64_t m, const uint32_t* row_of, const uint32_t* rank, const uint32_t* rank_bits,
+                            uint32_t build_last, int64_t* key_out, uint64_t key_min, hipStream_t s) {
+  if (m) hipLaunchKernelGGL(k_dense_translate, dim3(grid_for(m)), dim3(QH_BLOCK), 0, s, (const u32*)keys, (u32*)rows, (u64)m, (const u32*)row_of,
+                            (const u32*)rank, (const u32*)rank_bits, (u32)build_last, (i64*)key_out, (u64)key_min);
+}
 void launch_lower_bound_u32(const uint32_t* a, uint64_t m, const uint32_t* m_dev, const uint64_t* bound, uint32_t nb, uint32_t* pos, hipStream_t s) {
   if (nb) hipLaunchKernelGGL(k_lower_bound_u32, dim3((nb + QH_BLOCK - 1) / QH_BLOCK), dim3(QH_BLOCK), 0, s, (const u32*)a, (u64)m, (const u32*)m_dev, (const u64*)bound, nb, (u32*)pos);
 }
@@ -1335,12 +1393,17 @@ void launch_join_emit(const uint32_t* ent_slot, const uint32_t* ent_row, const u
                       const uint32_t* start, const uint32_t* rows, const uint32_t* row_of, uint64_t nchunks, uint64_t chunk_rows, uint32_t* b_idx, uint32_t* p_idx,
                       uint32_t* pair_off, uint32_t* cnt_out, uint32_t* visited, uint32_t cap, const uint32_t* stat_block, uint32_t* publish,
                       uint32_t* rows_out, hipStream_t s, int64_t* key_out, uint64_t key_min, const uint32_t* rank, const uint32_t* rank_bits,
-                      uint32_t build_last) {
+                      uint32_t build_last, bool fold_scan) {
   if (!nchunks) return;
-  hipLaunchKernelGGL(k_join_emit, dim3(grid_for(nchunks * 64, QH_BLOCK)), dim3(QH_BLOCK), 0, s, (const u32*)ent_slot, (const u32*)ent_row,
+  const unsigned grid = grid_for(nchunks * 64, QH_BLOCK);
+  // (the folded scan reads the counters with 16-byte loads and gives every workgroup ONE base: its chunks are one trip of the loop)
+  if (fold_scan && (!join_emit_can_fold(nchunks, chunk_off) || !stat_block || (uint64_t)grid * (QH_BLOCK / 64) < nchunks))
+    fail(QHIP_INVALID_ARGUMENT, "join pass 2: the chunk counters cannot be summed in the launch (internal error)");
+  hipLaunchKernelGGL(k_join_emit, dim3(grid), dim3(QH_BLOCK), 0, s, (const u32*)ent_slot, (const u32*)ent_row,
                      (const u32*)chunk_nent, (const u32*)chunk_off, (const u32*)count, (const u32*)start, (const u32*)rows, (const u32*)row_of, (u64)nchunks,
                      (u64)chunk_rows, (u32*)b_idx, (u32*)p_idx, (u32*)pair_off, (u32*)cnt_out, (u32*)visited, (u32)cap, (const u32*)stat_block,
-                     (u32*)publish, (u32*)rows_out, (i64*)key_out, (u64)key_min, (const u32*)rank, (const u32*)rank_bits, (u32)build_last);
+                     (u32*)publish, (u32*)rows_out, (i64*)key_out, (u64)key_min, (const u32*)rank, (const u32*)rank_bits, (u32)build_last,
+                     fold_scan ? 1u : 0u);
 }
 void launch_join_mark(const uint32_t* b_idx, const uint32_t* p_idx, uint64_t m, uint32_t* visited_bits, uint32_t* cnt_per_probe, hipStream_t s) {
   if (!m) return;

@@ -334,6 +334,8 @@ bool key_range_of(Ctx* ctx, const DevColumn& col_in, int64_t& mn, int64_t& mx) {
   const DevColumn* col = &col_in;
   if (!col->range->known) {
     if (col->pending_upload) col = &resolved(ctx, *col);
+    // (a dense join's owed key column is a plain column once written, with values of its own to look at: no source to ask)
+    if (col->deferred && !col->deferred->done && col->deferred->key_of) col = &resolved(ctx, *col);
     const DevColumn* base = col;
     if (col->deferred && !col->deferred->done) {
       DevColumn& src = col->deferred->src;
@@ -375,7 +377,7 @@ bool key_range_of(Ctx* ctx, const DevColumn& col_in, int64_t& mn, int64_t& mx) {
 bool key_ascending(Ctx* ctx, const DevColumn& col) {
   int64_t mn = 0, mx = 0;
   if (!key_range_of(ctx, col, mn, mx)) return false;
-  if (col.deferred && !col.deferred->done) {
+  if (col.deferred && !col.deferred->done && !col.deferred->key_of) {
     const DeferredGather& d = *col.deferred;
     return d.idx_ascends && !d.idx_may_be_null && d.src.range->known && d.src.range->ascending &&
            (!d.src.range_inherited || d.src.range_order);
@@ -401,8 +403,25 @@ const DevColumn& resolved(Ctx* ctx, const DevColumn& col) {
   }
   if (!col.deferred) return col;
   DeferredGather& d = *col.deferred;
+  if (!d.done && d.key_of) {
+    // a dense join's key column: key_min + the key index of every row, a plain Int64 column from here on
+    const uint64_t room = std::max<uint64_t>(d.key_of->m, d.m);
+    const uint32_t* keys = index_rows(ctx, d.key_of);
+    DevColumn out;
+    out.type = d.src.type;
+    out.length = (int64_t)d.m;
+    out.value_maxabs = d.src.value_maxabs;
+    out.range = d.src.range; out.range_inherited = true;   // (a subset of the source's values: its bounds hold)
+    out.values = std::make_shared<DevBuf>((room + 1) * 8);
+    launch_dense_translate(keys, nullptr, std::min<uint64_t>(d.key_of->m, room), nullptr, nullptr, nullptr, 0, out.values->as<int64_t>(), (uint64_t)d.key_min, ctx->stream);
+    ++ctx->lazy_key_columns;
+    d.result = std::move(out);
+    d.done = true;
+    d.src = DevColumn();
+    d.key_of.reset();
+  }
   if (!d.done) {
-    d.result = gather_column(ctx, d.src, d.idx->as<uint32_t>(), d.m, d.idx_may_be_null);
+    d.result = gather_column(ctx, d.src, index_rows(ctx, d.idx), d.m, d.idx_may_be_null);
     d.result.range_order = d.idx_ascends && !d.idx_may_be_null && (!d.src.range_inherited || d.src.range_order);
     d.done = true;
     d.src = DevColumn();   // the source buffers and the index vector are no longer needed by this column
@@ -421,23 +440,86 @@ void resolve_all(Ctx* ctx, const qhip_table* t) {
   for (const DevColumn& c : t->cols) (void)resolved(ctx, c);
 }
 
+// The rows of an index vector, looked up or composed now if they were owed — once: every column and every table that shares
+// the object finds them afterwards. A pending part that is itself pending is resolved first (chains of joins).
+const uint32_t* index_rows(Ctx* ctx, const std::shared_ptr<LazyIndex>& xp) {
+  if (!xp) fail(QHIP_HIP_ERROR, "a deferred gather without an index vector (internal error)");
+  LazyIndex& x = *xp;
+  if (x.rows) return x.rows->as<uint32_t>();
+  auto rows = std::make_shared<DevBuf>((x.m + 1) * 4);
+  if (x.keys) {
+    const uint32_t* keys = index_rows(ctx, x.keys);
+    launch_dense_translate(keys, rows->as<uint32_t>(), std::min(x.m, x.keys->m), x.row_of, x.rank, x.rank_bits, x.build_last, nullptr, 0, ctx->stream);
+    ++ctx->index_translations;
+    // (the launch holds raw pointers: the key indices and the table may go only now — stream-ordered pool)
+    x.keys.reset();
+    x.table.reset();
+    x.row_of = x.rank = x.rank_bits = nullptr;
+  } else if (x.inner && x.outer) {
+    const uint32_t* inner = index_rows(ctx, x.inner);
+    const uint32_t* outer = index_rows(ctx, x.outer);
+    launch_gather_u32_nullable(inner, outer, rows->as<uint32_t>(), std::min(x.m, x.outer->m), ctx->stream);
+    ++ctx->index_compositions;
+    x.inner.reset();
+    x.outer.reset();
+  } else {
+    fail(QHIP_HIP_ERROR, "an index vector that is neither ready nor owed (internal error)");
+  }
+  x.rows = rows;
+  return x.rows->as<uint32_t>();
+}
+
+int index_state(const DevColumn& c) {
+  if (!c.deferred || c.deferred->done) return 0;
+  const DeferredGather& d = *c.deferred;
+  if (d.key_of) return 4;
+  if (!d.idx) return 0;
+  return d.idx->rows ? 1 : d.idx->keys ? 2 : 3;
+}
+
 void defer_gather(Ctx* ctx, const std::vector<DevColumn>& cols, const std::shared_ptr<DevBuf>& idx, uint64_t m, bool idx_may_be_null,
                   std::vector<DevColumn>& out, bool idx_ascends) {
-  std::vector<std::pair<const DevBuf*, std::shared_ptr<DevBuf>>> composed;   // inner index vector -> inner[idx]
-  // the compositions (one per distinct inner index vector) go into ONE launch
-  {
+  defer_gather(ctx, cols, LazyIndex::of(idx, m), m, idx_may_be_null, out, idx_ascends);
+}
+
+void defer_gather(Ctx* ctx, const std::vector<DevColumn>& cols, const std::shared_ptr<LazyIndex>& idx, uint64_t m, bool idx_may_be_null,
+                  std::vector<DevColumn>& out, bool idx_ascends) {
+  const bool lazy = env_int("QHIP_JOIN_LAZY_INDEX", 1) != 0;
+  // a column's value through `idx`: an owed key column of a dense join below stays owed (its key indices are composed like an
+  // index vector) unless a NULL index could reach it — a NULL key index has no value, so that column is written first
+  for (const DevColumn& c : cols)
+    if (c.deferred && !c.deferred->done && c.deferred->key_of && (idx_may_be_null || !lazy)) (void)resolved(ctx, c);
+  std::vector<std::pair<const LazyIndex*, std::shared_ptr<LazyIndex>>> composed;   // inner index vector -> inner[idx]
+  auto inner_of = [](const DevColumn& c) -> const std::shared_ptr<LazyIndex>& { return c.deferred->key_of ? c.deferred->key_of : c.deferred->idx; };
+  if (lazy) {
+    // the compositions are OWED too, one per distinct inner index vector: a group of columns nobody reads costs nothing, a group
+    // that is read is composed at its first read (index_rows)
+    for (const DevColumn& c : cols) {
+      if (!(c.deferred && !c.deferred->done)) continue;
+      const std::shared_ptr<LazyIndex>& in = inner_of(c);
+      bool seen = false;
+      for (auto& e : composed) seen = seen || e.first == in.get();
+      if (seen) continue;
+      auto both = std::make_shared<LazyIndex>();
+      both->m = m; both->inner = in; both->outer = idx;
+      composed.emplace_back(in.get(), both);
+    }
+  } else {
+    // QHIP_JOIN_LAZY_INDEX=0: composed now, the compositions (one per distinct inner index vector) in ONE launch
+    const uint32_t* rows = index_rows(ctx, idx);
     GatherBatch gb;
     memset(&gb, 0, sizeof gb);
+    std::vector<std::shared_ptr<LazyIndex>> keep;
     int n = 0;
     for (const DevColumn& c : cols) {
       if (!(c.deferred && !c.deferred->done)) continue;
-      const DeferredGather& in = *c.deferred;
+      const std::shared_ptr<LazyIndex>& in = inner_of(c);
       bool seen = false;
-      for (auto& e : composed) seen = seen || e.first == in.idx.get();
+      for (auto& e : composed) seen = seen || e.first == in.get();
       if (seen || n >= kGatherBatch) continue;
       auto both = std::make_shared<DevBuf>((m + 1) * 4);
-      gb.d[n++] = GatherDesc{in.idx->ptr, idx->as<uint32_t>(), both->ptr, m, 4u, 1u};
-      composed.emplace_back(in.idx.get(), both);
+      gb.d[n++] = GatherDesc{index_rows(ctx, in), rows, both->ptr, m, 4u, 1u};
+      composed.emplace_back(in.get(), LazyIndex::of(both, m));
     }
     if (n == 1) launch_gather_u32_nullable((const uint32_t*)gb.d[0].in, gb.d[0].idx, (uint32_t*)gb.d[0].out, m, ctx->stream);
     else if (n > 1) launch_gather_multi(gb, n, ctx->stream);
@@ -453,15 +535,18 @@ void defer_gather(Ctx* ctx, const std::vector<DevColumn>& cols, const std::share
     d->m = m;
     if (c.deferred && !c.deferred->done) {
       const DeferredGather& in = *c.deferred;
-      std::shared_ptr<DevBuf> both;
-      for (auto& e : composed) if (e.first == in.idx.get()) both = e.second;
-      if (!both) {
-        both = std::make_shared<DevBuf>((m + 1) * 4);
-        launch_gather_u32_nullable(in.idx->as<uint32_t>(), idx->as<uint32_t>(), both->as<uint32_t>(), m, ctx->stream);
-        composed.emplace_back(in.idx.get(), both);
+      const std::shared_ptr<LazyIndex>& in_idx = inner_of(c);
+      std::shared_ptr<LazyIndex> both;
+      for (auto& e : composed) if (e.first == in_idx.get()) both = e.second;
+      if (!both) {   // (more distinct inner vectors than one launch takes)
+        auto buf = std::make_shared<DevBuf>((m + 1) * 4);
+        launch_gather_u32_nullable(index_rows(ctx, in_idx), index_rows(ctx, idx), buf->as<uint32_t>(), m, ctx->stream);
+        both = LazyIndex::of(buf, m);
+        composed.emplace_back(in_idx.get(), both);
       }
       d->src = in.src;
-      d->idx = both;
+      if (in.key_of) { d->key_of = both; d->key_min = in.key_min; }
+      else d->idx = both;
       d->idx_may_be_null = in.idx_may_be_null || idx_may_be_null;
       d->idx_ascends = in.idx_ascends && idx_ascends;   // (an ascending vector read through an ascending one ascends)
     } else {
@@ -522,7 +607,7 @@ void resolve_referenced(Ctx* ctx, const qhip_table* t, const qhip_expr* exprs, i
         out.range_order = d.idx_ascends && !d.idx_may_be_null && (!d.src.range_inherited || d.src.range_order);
         const int w = dtype_width(d.src.type);
         out.values = std::make_shared<DevBuf>((size_t)d.m * (size_t)w);
-        gb.d[j] = GatherDesc{d.src.values->ptr, d.idx->as<uint32_t>(), out.values->ptr, d.m, (uint32_t)w, 0u};
+        gb.d[j] = GatherDesc{d.src.values->ptr, index_rows(ctx, d.idx), out.values->ptr, d.m, (uint32_t)w, 0u};
         d.result = std::move(out);
       }
       launch_gather_multi(gb, n, ctx->stream);

@@ -36,6 +36,15 @@ const DevColumn& resolved(Ctx* ctx, const DevColumn& col);
 // read. Deferred inputs are composed (one u32 gather per distinct inner index vector), never chained.
 void defer_gather(Ctx* ctx, const std::vector<DevColumn>& cols, const std::shared_ptr<DevBuf>& idx, uint64_t m, bool idx_may_be_null,
                   std::vector<DevColumn>& out, bool idx_ascends = false);
+// ... through an index vector that may itself be owed (LazyIndex): the compositions with deferred inputs are then owed too, one per
+// distinct inner vector, and made when a column of the group is first read (QHIP_JOIN_LAZY_INDEX=0: composed at once)
+void defer_gather(Ctx* ctx, const std::vector<DevColumn>& cols, const std::shared_ptr<LazyIndex>& idx, uint64_t m, bool idx_may_be_null,
+                  std::vector<DevColumn>& out, bool idx_ascends = false);
+// THE access to a deferred gather's index vector: its u32 rows, looked up (a dense join's key indices) or composed (inner[outer])
+// now if they were owed; once for everybody sharing the object
+const uint32_t* index_rows(Ctx* ctx, const std::shared_ptr<LazyIndex>& idx);
+// 0 = not a pending gather, 1 = its index vector is ready, 2 = pending translation, 3 = pending composition, 4 = an owed join key column
+int index_state(const DevColumn& c);
 void resolve_all(Ctx* ctx, const qhip_table* t);
 // gather the columns the expression trees reference (everything else may stay deferred)
 void resolve_referenced(Ctx* ctx, const qhip_table* t, const qhip_expr* exprs, int n_exprs, bool keep_indirect = false);

@@ -305,6 +305,42 @@ def sorted_build_counts(ctx) -> Tuple[int, int]:
     return int(a.value), int(b.value)
 
 
+def join_scan_counts(ctx) -> Tuple[int, int]:
+    """qhip_ctx_join_scan_counts: (hash join probes whose pass 2 summed the chunk counters itself, probes whose counters were
+    scanned in a launch of their own)"""
+    fn = ctx.lib.qhip_ctx_join_scan_counts
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    a, b = C.c_int64(), C.c_int64()
+    ctx.check(fn(ctx.handle, C.byref(a), C.byref(b)))
+    return int(a.value), int(b.value)
+
+
+def lazy_index_counts(ctx) -> Tuple[int, int, int, int]:
+    """qhip_ctx_lazy_index_counts: (joins that left their build-side index vector owed, such vectors translated after all, index
+    compositions made at a first read, owed join key columns written after all)"""
+    fn = ctx.lib.qhip_ctx_lazy_index_counts
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+    out = (C.c_int64 * 4)()
+    ctx.check(fn(ctx.handle, out))
+    return tuple(int(v) for v in out)
+
+
+INDEX_NOTHING, INDEX_READY, INDEX_PENDING_TRANSLATION, INDEX_PENDING_COMPOSITION, INDEX_PENDING_KEY = range(5)
+
+
+def column_index_state(table: DeviceTable, col: int) -> int:
+    """qhip_table_column_index_state: what column `col` still owes (INDEX_*); launches nothing"""
+    ctx = table.ctx
+    fn = ctx.lib.qhip_table_column_index_state
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p, C.c_int64, C.POINTER(C.c_int32)]
+    out = C.c_int32()
+    ctx.check(fn(table.handle, int(col), C.byref(out)))
+    return int(out.value)
+
+
 class qhip_shuffle_input(C.Structure):
     _fields_ = [("table", C.c_void_p), ("exprs", C.POINTER(_ffi.qhip_expr)), ("n_exprs", C.c_int32), ("key_roots", C.POINTER(C.c_int32)),
                 ("n_keys", C.c_int32), ("predicate_root", C.c_int32), ("all_gather", C.c_int32), ("keep_columns", C.POINTER(C.c_int32)),
