@@ -379,7 +379,7 @@ int qhip_ctx_json_pass_ms(const qhip_ctx* ctx, double* out, int32_t n_out);
  * writes by default: their pages cross PCIe compressed and are unpacked on the device; a page whose stream is damaged, or which
  * claims more than 64/3 times its compressed size, needs the host ("Snappy").
  * Needs the host: a compressed projected chunk (level 1: every codec, so write with compression="NONE" or set level 2; level 2:
- * every codec but SNAPPY — zstd, gzip, lz4, brotli), data pages V2 (encoding set 1; qhip_ctx_set_parquet_encodings below), index
+ * every codec but SNAPPY — zstd, gzip, lz4, brotli; codec set 2, qhip_ctx_set_parquet_codecs below, takes ZSTD), data pages V2 (encoding set 1; qhip_ctx_set_parquet_encodings below), index
  * pages, an encrypted footer, a group / list / map field anywhere in the schema, a chunk with file_path, any other encoding
  * (DELTA_*, BYTE_STREAM_SPLIT, RLE values; encoding set 2 decodes these but DELTA_BYTE_ARRAY), BIT_PACKED levels, every other type pair (a zoned Timestamp, Date64, Time, Float16,
  * Decimal256, INT96, LargeUtf8, Binary, dictionary-typed fields), a stored value outside an Int8/Int16/UInt8/UInt16 column's
@@ -391,9 +391,10 @@ int qhip_table_from_parquet(qhip_ctx* ctx, const struct ArrowSchema* schema, con
 /* Device time (ms) of the last qhip_table_from_parquet's five passes — upload, levels, string walk, values, Utf8 — when the
  * context's timing is on (qhip_ctx_set_timing); zeros otherwise. n_out must be 5. */
 int qhip_ctx_parquet_pass_ms(const qhip_ctx* ctx, double* out, int32_t n_out);
-/* Device time (ms) of the unpack pass (format level 2: Snappy pages -> the unpack area) of the last qhip_table_from_parquet, or of
- * the last qhip_snappy_decode's kernel, when the context's timing is on; 0 otherwise and for a file without Snappy pages. The
- * pass runs between "upload" and "levels" and belongs to neither of qhip_ctx_parquet_pass_ms's five values. */
+/* Device time (ms) of the unpack passes (format level 2: Snappy pages, codec set 2: ZSTD pages -> the unpack area) of the last
+ * qhip_table_from_parquet, or of the last qhip_snappy_decode's or qhip_zstd_decode's kernel, when the context's timing is on; 0
+ * otherwise and for a file without Snappy or ZSTD pages. The passes run between "upload" and "levels" and belong to neither of
+ * qhip_ctx_parquet_pass_ms's five values. */
 int qhip_ctx_parquet_unpack_ms(const qhip_ctx* ctx, double* out);
 /* The format qhip_table_from_parquet decodes. level 1 (the default): uncompressed chunks only. level 2: also SNAPPY chunks,
  * unpacked by a kernel of its own — a file without them launches what level 1 launches. Any other level answers
@@ -415,6 +416,19 @@ int qhip_ctx_set_parquet_format(qhip_ctx* ctx, int32_t level);
  * Any other set answers QHIP_INVALID_ARGUMENT and leaves the set as it was. The environment's QHIP_PARQUET_ENCODINGS (1 / 2) is
  * read when the context is created. */
 int qhip_ctx_set_parquet_encodings(qhip_ctx* ctx, int32_t set);
+/* The codecs qhip_table_from_parquet unpacks on the device, a switch of its own next to the format level and the encoding set.
+ * set 1 (the default): the codecs the format level admits, nothing else. set 2: also projected chunks whose codec is ZSTD
+ * (Parquet codec 6). SNAPPY stays with the format level: a file with Snappy and ZSTD columns needs level 2 and codec set 2, a
+ * ZSTD file with data pages V2 codec set 2 and encoding set 2. A ZSTD page is one Zstandard frame (RFC 8878), decoded whole by a
+ * kernel of its own, one wavefront per page: raw, RLE and compressed blocks, Huffman literals in one or four streams, FSE
+ * tables in every mode, repeat offsets. The host reads the frame header and the chain of block headers before anything is
+ * reserved and sends to the host path ("Zstd") a frame with a dictionary id, the reserved bit, a skippable or second frame,
+ * bytes behind the last block other than the 4 checksum bytes, a block of the reserved type or above 128 KB, a
+ * Frame_Content_Size that differs from uncompressed_page_size, and an uncompressed_page_size the blocks cannot produce. The
+ * content checksum is skipped, not verified, and Window_Size is not enforced: an offset may reach the page's first byte. A
+ * file without ZSTD chunks launches what set 1 launches. Any other set answers QHIP_INVALID_ARGUMENT and leaves the set as it
+ * was. The environment's QHIP_PARQUET_CODECS (1 / 2) is read when the context is created. */
+int qhip_ctx_set_parquet_codecs(qhip_ctx* ctx, int32_t set);
 /* Device time (ms) of the delta pass (encoding set 2: DELTA_* pages -> the decoded area) of the last qhip_table_from_parquet, or
  * of the last qhip_parquet_delta_decode's kernel, when the context's timing is on; 0 otherwise and for a file without such
  * pages. The pass runs between "levels" and "string walk" and belongs to neither of qhip_ctx_parquet_pass_ms's five values. */
@@ -438,6 +452,11 @@ int qhip_parquet_delta_decode(qhip_ctx* ctx, const void* bytes, int64_t n_bytes,
  * is a normal return, its bytes in out are unspecified, and the other streams of the call are decoded all the same. */
 int qhip_snappy_decode(qhip_ctx* ctx, const void* bytes, int64_t n_bytes, const int64_t* src_offsets, const int64_t* dst_sizes,
                        int64_t n_streams, void* out, int64_t out_bytes, int32_t* status);
+/* A testing and measurement aid with the signature and contract of qhip_snappy_decode: the device Zstandard decoder of codec
+ * set 2 over raw frames, as a Parquet page holds them. The checks made first are the page walk's (the frame header, the chain of
+ * block headers, the declared size against Frame_Content_Size and the blocks' bound); status[k]: 0 or a QH_PQ_R_ZSTD_*. */
+int qhip_zstd_decode(qhip_ctx* ctx, const void* bytes, int64_t n_bytes, const int64_t* src_offsets, const int64_t* dst_sizes,
+                     int64_t n_streams, void* out, int64_t out_bytes, int32_t* status);
 /* Download batch `batch_index` as a struct ArrowArray (+ schema if out_schema != NULL).
  * Buffers are library-owned host memory freed by the release callbacks.
  * batch_index == -1: every row of the table as ONE array — a caller facing thousands of small batches (the reference's

@@ -50,6 +50,7 @@ class Context {
   // the device Parquet decoder's encoding set (qhip.h: 1 pages V1 with PLAIN or dictionary values, 2 also pages V2, RLE Booleans,
   // BYTE_STREAM_SPLIT, DELTA_BINARY_PACKED and DELTA_LENGTH_BYTE_ARRAY)
   void set_parquet_encodings(int set) const { check(qhip_ctx_set_parquet_encodings(ctx_, set)); }
+  void set_parquet_codecs(int set) const { check(qhip_ctx_set_parquet_codecs(ctx_, set)); }
 
  private:
   qhip_ctx* ctx_ = nullptr;

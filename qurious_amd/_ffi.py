@@ -158,6 +158,8 @@ def load_library() -> C.CDLL:
             "qhip_ctx_set_parquet_format": (C.c_int, [vp, i32]),
             "qhip_snappy_decode": (C.c_int, [vp, vp, i64, P(i64), P(i64), i64, vp, i64, P(i32)]),
             "qhip_ctx_set_parquet_encodings": (C.c_int, [vp, i32]),
+            "qhip_ctx_set_parquet_codecs": (C.c_int, [vp, i32]),
+            "qhip_zstd_decode": (C.c_int, [vp, vp, i64, P(i64), P(i64), i64, vp, i64, P(i32)]),
             "qhip_ctx_parquet_delta_ms": (C.c_int, [vp, P(C.c_double)]),
             "qhip_parquet_delta_decode": (C.c_int, [vp, vp, i64, P(i64), P(i32), P(i64), i64, vp, i64, P(i64), P(i32)]),
             "qhip_table_to_arrow": (C.c_int, [vp, vp, i64, vp, vp]),
@@ -315,6 +317,13 @@ class Context:
         DELTA_LENGTH_BYTE_ARRAY. QHIP_PARQUET_ENCODINGS sets it when the context is made."""
         self.check(self.lib.qhip_ctx_set_parquet_encodings(self.handle, int(encodings)))
 
+    def set_parquet_codecs(self, codecs: int):
+        """The device Parquet decoder's codec set, independent of the format level and the encoding set: 1 (the default) the
+        codecs the format level admits; 2 also ZSTD chunks, each page a Zstandard frame decoded by a kernel of its own (the
+        content checksum is not verified). SNAPPY stays with the format level. QHIP_PARQUET_CODECS sets it when the context is
+        made."""
+        self.check(self.lib.qhip_ctx_set_parquet_codecs(self.handle, int(codecs)))
+
     def parquet_delta_ms(self) -> float:
         """Device time (ms) of the delta pass (k_pq_delta, encoding set 2) of the last device Parquet decode, or of the last
         `delta_decode`'s kernel (timing on). It lies between "levels" and "string walk" and is part of neither."""
@@ -351,11 +360,21 @@ class Context:
             at += nb
         return values, [int(ends[k]) for k in range(n)], [int(status[k]) for k in range(n)]
 
+    def zstd_decode(self, streams: Sequence[bytes], dst_sizes: Sequence[int]):
+        """A testing and measurement aid (qhip_zstd_decode): raw Zstandard frames through the device decoder of codec set 2, one
+        wavefront each, in one call. `dst_sizes[k]`: the uncompressed size declared for frame k. Returns (outputs, statuses):
+        statuses[k] is 0 or the needs-host reason (QH_PQ_R_ZSTD_*) for which frame k was refused, outputs[k] its bytes (None
+        when refused)."""
+        return self._unpack_decode(self.lib.qhip_zstd_decode, streams, dst_sizes)
+
     def snappy_decode(self, streams: Sequence[bytes], dst_sizes: Sequence[int]):
         """A testing and measurement aid (qhip_snappy_decode): raw Snappy streams through the device decoder of format level 2,
         one wavefront each, in one call. `dst_sizes[k]`: the uncompressed size declared for stream k. Returns (outputs, statuses):
         statuses[k] is 0 or the needs-host reason (QH_PQ_R_SNAPPY_*) for which stream k was refused, outputs[k] its bytes
         (None when refused)."""
+        return self._unpack_decode(self.lib.qhip_snappy_decode, streams, dst_sizes)
+
+    def _unpack_decode(self, entry, streams: Sequence[bytes], dst_sizes: Sequence[int]):
         n = len(streams)
         data = b"".join(streams)
         off = (C.c_int64 * (n + 1))()
@@ -365,7 +384,7 @@ class Context:
         total = sum(int(v) for v in dst_sizes if 0 <= int(v) <= 0x7FFFFFFF)
         out = C.create_string_buffer(max(total, 1))
         status = (C.c_int32 * max(n, 1))()
-        self.check(self.lib.qhip_snappy_decode(self.handle, data, len(data), off, dst, n, out, total, status))
+        self.check(entry(self.handle, data, len(data), off, dst, n, out, total, status))
         outs, at, raw = [], 0, out.raw
         for k in range(n):
             outs.append(raw[at:at + int(dst_sizes[k])] if status[k] == 0 else None)

@@ -74,7 +74,19 @@ typedef long long pq_i64;
 #define QH_PQ_R_DELTA_SHORT 45     // the stream ends inside its header, a block header, the width bytes or a miniblock
 #define QH_PQ_R_DELTA_WIDTH 46     // a miniblock that holds a value has a bit width above the type's
 #define QH_PQ_R_DELTA_LENGTH 47    // DELTA_LENGTH_BYTE_ARRAY: a negative length, or lengths that add up past the page
-#define QH_PQ_R_COUNT 48
+// (codec set 2, qhip_ctx_set_parquet_codecs: a ZSTD page, device/qhip_zstd.inc. QH_PQ_R_ZSTD_BASE + QH_ZSTD_E_*)
+#define QH_PQ_R_ZSTD_BASE 47
+#define QH_PQ_R_ZSTD_FRAME 48      // the frame header: magic, a dictionary id, the reserved bit, a skippable or second frame, stray bytes behind the last block
+#define QH_PQ_R_ZSTD_SIZE 49       // Frame_Content_Size or the blocks' bound against uncompressed_page_size
+#define QH_PQ_R_ZSTD_BLOCK 50      // a block header: cut off, the reserved type, above 128 KB, past the payload
+#define QH_PQ_R_ZSTD_LITERALS 51   // a literals section that is cut off, above 128 KB, or whose stream sizes do not fit
+#define QH_PQ_R_ZSTD_HUFFMAN 52    // a Huffman tree description outside the format's rules, or a treeless section without a tree
+#define QH_PQ_R_ZSTD_FSE 53        // an FSE table description outside the format's rules
+#define QH_PQ_R_ZSTD_SEQUENCES 54  // a sequences section that is cut off, has reserved bits, repeats a table that is not there, or wants more literals than there are
+#define QH_PQ_R_ZSTD_BITS 55       // a backward bit stream that underflows or does not end exactly at its start
+#define QH_PQ_R_ZSTD_OUTPUT 56     // output past uncompressed_page_size, or a frame that ends with output missing
+#define QH_PQ_R_ZSTD_OFFSET 57     // a match offset of 0 or beyond the bytes produced
+#define QH_PQ_R_COUNT 58
 
 QH_PQ_HD inline const char* qh_pq_reason_text(unsigned r) {
   switch (r) {
@@ -125,6 +137,16 @@ QH_PQ_HD inline const char* qh_pq_reason_text(unsigned r) {
     case QH_PQ_R_DELTA_SHORT: return "corrupt: a DELTA_BINARY_PACKED stream that ends inside a header or a miniblock";
     case QH_PQ_R_DELTA_WIDTH: return "corrupt: a DELTA_BINARY_PACKED bit width above the type's bits";
     case QH_PQ_R_DELTA_LENGTH: return "corrupt: a DELTA_LENGTH_BYTE_ARRAY length that is negative or points past its page";
+    case QH_PQ_R_ZSTD_FRAME: return "a Zstd page whose frame header is not one plain frame: magic, dictionary id, reserved bit, or bytes behind the last block";
+    case QH_PQ_R_ZSTD_SIZE: return "corrupt: a Zstd page whose frame size or block sizes do not fit uncompressed_page_size";
+    case QH_PQ_R_ZSTD_BLOCK: return "corrupt: a Zstd block header that is cut off, of the reserved type, above 128 KB or past its page";
+    case QH_PQ_R_ZSTD_LITERALS: return "corrupt: a Zstd literals section that is cut off, above 128 KB, or whose streams do not fit";
+    case QH_PQ_R_ZSTD_HUFFMAN: return "corrupt: a Zstd Huffman tree description outside the format's rules";
+    case QH_PQ_R_ZSTD_FSE: return "corrupt: a Zstd FSE table description outside the format's rules";
+    case QH_PQ_R_ZSTD_SEQUENCES: return "corrupt: a Zstd sequences section that is cut off or inconsistent with its literals and tables";
+    case QH_PQ_R_ZSTD_BITS: return "corrupt: a Zstd bit stream that underflows or does not end exactly at its start";
+    case QH_PQ_R_ZSTD_OUTPUT: return "corrupt: a Zstd page whose output passes or does not fill uncompressed_page_size";
+    case QH_PQ_R_ZSTD_OFFSET: return "corrupt: a Zstd match offset of 0 or beyond the bytes produced";
     default: return "outside the device's Parquet coverage";
   }
 }
@@ -180,7 +202,9 @@ typedef struct qh_pq_dstream {
 } qh_pq_dstream;
 #define QH_PQ_DS_LENGTHS 0x100u
 
-// one compressed page (format level 2): k_pq_unsnap turns buffer[src .. src + src_size) into buffer[dst .. dst + dst_size)
+// one compressed page (format level 2): k_pq_unsnap turns buffer[src .. src + src_size) into buffer[dst .. dst + dst_size).
+// Codec set 2 keeps the ZSTD pages in a second table of the same entries for k_pq_unzstd: `start` is then where the frame's
+// first block header lies, and dst_size what the frame header says where it says it.
 typedef struct qh_pq_unpack {
   pq_u64 src;         // the compressed payload, in the uploaded chunks
   pq_u64 dst;         // the page's slot in the unpack area, 16-byte aligned

@@ -5,6 +5,7 @@
 // The unit of parallelism is the page: one wavefront each. Serial work happens per run header and per BYTE_ARRAY length prefix
 // only; the values of a run are spread over the lanes.
 //   k_pq_unsnap   format level 2 only: a Snappy page of the uploaded chunks -> its uncompressed bytes in the unpack area
+//   k_pq_unzstd   codec set 2 only: a ZSTD page of the uploaded chunks -> its uncompressed bytes in the unpack area
 //   k_pq_levels   RLE / bit-packed definition levels -> validity words, the page's non-NULL count, the column's NULL count
 //   k_pq_strings  the length chain of a Utf8 dictionary page or PLAIN data page, staged through LDS -> (length, position)
 //   k_pq_delta    encoding set 2 only: a DELTA_BINARY_PACKED stream -> dense values in the decoded area, or a Utf8 page's entries
@@ -19,6 +20,7 @@
 #include "device/qhip_device.hpp"
 #include "kernels_parquet.hpp"
 #include "device/qhip_snappy.inc"
+#include "device/qhip_zstd.inc"
 
 namespace qhip {
 
@@ -206,6 +208,28 @@ __global__ __launch_bounds__(64) void k_pq_unsnap(u8* buf, u64 buf_bytes, const 
   if (lane == 0) {
     if (status) status[k] = reason;
     if (reason && err) pq_report(err, u.page, QH_PQ_R_SNAPPY_BASE + reason);
+  }
+}
+
+// Codec set 2: one wavefront (a workgroup of its own) unpacks one ZSTD page, a whole Zstandard frame, from the uploaded chunks
+// into its slot of the unpack area, both in `buf`. The decoder is device/qhip_zstd.inc, which says how: the walk over blocks,
+// table descriptions and sequences is wave-uniform, with the Huffman and FSE tables of the page in LDS (10 148 bytes, all lanes
+// storing the same cell); Huffman literals are decoded by up to four lanes, a stream each, into the tail of the page's own slot;
+// the bytes of a literal run and of a match are spread over the lanes, a match 64 bytes per step. Bytes that other lanes of the
+// wavefront stored are read back from global memory under the rule k_pq_unsnap rests on, so `buf` is neither const nor
+// __restrict__ here either. The host has checked the frame header and the chain of block headers (qh_zstd_check_frame); the
+// walk checks them again as it goes, and every length, count, accuracy, weight and offset before it is followed. The content
+// checksum is not verified. A refused page leaves its slot half written.
+__global__ __launch_bounds__(64) void k_pq_unzstd(u8* buf, const qh_pq_unpack* __restrict__ tab, u32 n, u64* err, u32* status) {
+  __shared__ qh_zs_tables T;
+  const u32 k = blockIdx.x;
+  if (k >= n) return;
+  const qh_pq_unpack u = tab[k];
+  const u32 lane = (u32)qh_lane();
+  const u32 reason = qh_zstd_frame(buf + u.src, u.src_size, u.start, buf + u.dst, u.dst_size, &T, lane);
+  if (lane == 0) {
+    if (status) status[k] = reason;
+    if (reason && err) pq_report(err, u.page, QH_PQ_R_ZSTD_BASE + reason);
   }
 }
 
@@ -479,6 +503,10 @@ void launch_pq_levels(const uint8_t* buf, const qh_pq_page* pages, uint32_t npag
 void launch_pq_unsnap(uint8_t* buf, uint64_t buf_bytes, const qh_pq_unpack* tab, uint32_t n, uint64_t* err, uint32_t* status, hipStream_t s) {
   if (!n) return;
   hipLaunchKernelGGL(k_pq_unsnap, dim3(n), dim3(64), 0, s, (u8*)buf, (u64)buf_bytes, tab, (u32)n, (u64*)err, (u32*)status);
+}
+void launch_pq_unzstd(uint8_t* buf, const qh_pq_unpack* tab, uint32_t n, uint64_t* err, uint32_t* status, hipStream_t s) {
+  if (!n) return;
+  hipLaunchKernelGGL(k_pq_unzstd, dim3(n), dim3(64), 0, s, (u8*)buf, tab, (u32)n, (u64*)err, (u32*)status);
 }
 void launch_pq_strings(const uint8_t* buf, uint64_t buf_bytes, const qh_pq_page* pages, uint32_t npages, const qh_pq_col* cols, const qh_pq_state* state, uint64_t* err,
                        hipStream_t s) {

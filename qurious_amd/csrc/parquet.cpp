@@ -8,12 +8,15 @@
 // are uploaded compressed and unpacked on the device into an unpack area behind the uploaded chunks in the same buffer, where
 // the passes below read them as they read any page. Encoding set 2 (qhip_ctx_set_parquet_encodings), independent of the level,
 // adds data pages V2, RLE Boolean values, BYTE_STREAM_SPLIT, DELTA_BINARY_PACKED and DELTA_LENGTH_BYTE_ARRAY: a pass in front
-// (k_pq_delta) leaves a delta page's values dense in a decoded area behind the unpack area. Whatever lies outside makes the whole call answer QHIP_UNSUPPORTED with nothing
+// (k_pq_delta) leaves a delta page's values dense in a decoded area behind the unpack area. Codec set 2
+// (qhip_ctx_set_parquet_codecs), independent of both, adds ZSTD chunks: their pages get slots in the same unpack area and a
+// kernel of their own (k_pq_unzstd, a whole Zstandard frame decoder; the content checksum is not verified). Whatever lies outside makes the whole call answer QHIP_UNSUPPORTED with nothing
 // created, and the caller takes the host path, which then produces every error message.
 //
 // Passes, all on the context's stream:
 //   1 upload        the projected chunks, one behind the other, into one device buffer; the page table and column descriptors
 //  (k_pq_unsnap    level 2, a file with Snappy pages only: one wavefront per page, into the unpack area)
+//  (k_pq_unzstd    codec set 2, a file with ZSTD pages only: one wavefront per page, into the unpack area)
 //   2 k_pq_levels   definition levels -> validity words, non-NULL count per page, NULL count per column
 //  (k_pq_delta     set 2, a file with DELTA_* pages only: one wavefront per page, into the decoded area or the column's entries)
 //   3 k_pq_strings  Utf8: the length chains of dictionary pages and PLAIN data pages -> (length, position) entries
@@ -68,7 +71,7 @@ qhip_table* table_from_parquet(Ctx* ctx, const ArrowSchema* schema, const uint8_
   // ---- footer and page walk (host, one header per page)
   qhip_pq::Plan plan;
   try {
-    plan = qhip_pq::plan_file(bytes, (uint64_t)n_bytes, &names, types, proj, ctx->parquet_format, ctx->parquet_encodings);
+    plan = qhip_pq::plan_file(bytes, (uint64_t)n_bytes, &names, types, proj, ctx->parquet_format, ctx->parquet_encodings, ctx->parquet_codecs);
   } catch (const qhip_pq::PqNeedsHost& e) {
     fail(QHIP_UNSUPPORTED, qhip_pq::needs_host_text(e));
   }
@@ -156,18 +159,21 @@ qhip_table* table_from_parquet(Ctx* ctx, const ArrowSchema* schema, const uint8_
   DevBuf unpack_d;
   if (nunpack) unpack_d.alloc((size_t)nunpack * sizeof(qh_pq_unpack));
   if (nunpack) QHIP_HIP_CHECK(hipMemcpyAsync(unpack_d.ptr, plan.unpack.data(), (size_t)nunpack * sizeof(qh_pq_unpack), hipMemcpyHostToDevice, ctx->stream));
+  const uint32_t nunzstd = (uint32_t)plan.unzstd.size();
+  DevBuf unzstd_d;
+  if (nunzstd) unzstd_d.alloc((size_t)nunzstd * sizeof(qh_pq_unpack));
+  if (nunzstd) QHIP_HIP_CHECK(hipMemcpyAsync(unzstd_d.ptr, plan.unzstd.data(), (size_t)nunzstd * sizeof(qh_pq_unpack), hipMemcpyHostToDevice, ctx->stream));
   const uint32_t ndelta = (uint32_t)plan.delta.size();
   DevBuf delta_d;
   if (ndelta) delta_d.alloc((size_t)ndelta * sizeof(qh_pq_dstream));
   if (ndelta) QHIP_HIP_CHECK(hipMemcpyAsync(delta_d.ptr, plan.delta.data(), (size_t)ndelta * sizeof(qh_pq_dstream), hipMemcpyHostToDevice, ctx->stream));
   mark(1);
 
-  // ---- level 2: the Snappy pages into their slots
+  // ---- level 2: the Snappy pages into their slots; codec set 2: the ZSTD pages into theirs
   time_mark(ctx, 2);
-  if (nunpack) {
-    launch_pq_unsnap(file.as<uint8_t>(), buf_bytes, unpack_d.as<qh_pq_unpack>(), nunpack, st_dev + kUnpackWord, nullptr, ctx->stream);
-    mark(6);
-  }
+  if (nunpack) launch_pq_unsnap(file.as<uint8_t>(), buf_bytes, unpack_d.as<qh_pq_unpack>(), nunpack, st_dev + kUnpackWord, nullptr, ctx->stream);
+  if (nunzstd) launch_pq_unzstd(file.as<uint8_t>(), unzstd_d.as<qh_pq_unpack>(), nunzstd, st_dev + kUnpackWord, nullptr, ctx->stream);
+  if (nunpack || nunzstd) mark(6);
 
   // ---- 2 .. 4: levels, string walk, values
   launch_pq_levels(file.as<uint8_t>(), pages_d.as<qh_pq_page>(), npages, cols_d.as<qh_pq_col>(), state_d.as<qh_pq_state>(), st_dev, st_dev + 1, ctx->stream);
@@ -217,7 +223,7 @@ qhip_table* table_from_parquet(Ctx* ctx, const ArrowSchema* schema, const uint8_
   if (ctx->timing) {
     QHIP_HIP_CHECK(sync_event(ev[5]));
     for (int k = 0; k < 5; ++k) (void)hipEventElapsedTime(&ctx->parquet_pass_ms[k], ev[k], ev[k + 1]);
-    if (ev[6]) {   // "levels" begins behind the unpack pass, "upload" stays the upload
+    if (ev[6]) {   // "levels" begins behind the unpack passes, "upload" stays the upload
       (void)hipEventElapsedTime(&ctx->parquet_unpack_ms, ev[1], ev[6]);
       (void)hipEventElapsedTime(&ctx->parquet_pass_ms[1], ev[6], ev[2]);
     }
@@ -241,26 +247,30 @@ qhip_table* table_from_parquet(Ctx* ctx, const ArrowSchema* schema, const uint8_
   return t.release();
 }
 
-// qhip_snappy_decode: k_pq_unsnap over raw streams, with the checks the page walk makes of a page's sizes. A refused stream is
-// an answer (status), not an error.
-void snappy_decode(Ctx* ctx, const uint8_t* bytes, int64_t n_bytes, const int64_t* src_offsets, const int64_t* dst_sizes, int64_t n_streams, uint8_t* out,
-                   int64_t out_bytes, int32_t* status) {
+// qhip_snappy_decode / qhip_zstd_decode: k_pq_unsnap / k_pq_unzstd over raw streams, with the checks the page walk makes of a
+// page's sizes (of a ZSTD page: its frame header and block headers). A refused stream is an answer (status), not an error.
+static void unpack_decode(Ctx* ctx, bool zstd, const uint8_t* bytes, int64_t n_bytes, const int64_t* src_offsets, const int64_t* dst_sizes, int64_t n_streams,
+                          uint8_t* out, int64_t out_bytes, int32_t* status) {
+  const std::string fn = zstd ? "qhip_zstd_decode" : "qhip_snappy_decode";
+  const int reason_base = zstd ? QH_PQ_R_ZSTD_BASE : QH_PQ_R_SNAPPY_BASE;
   uint64_t total_out = 0;
   for (int64_t k = 0; k < n_streams; ++k) {
     const int64_t a = src_offsets[k], b = src_offsets[k + 1];
     if (a < 0 || b < a || b > n_bytes || b - a > 0x7FFFFFFF || dst_sizes[k] < 0 || dst_sizes[k] > 0x7FFFFFFF)
-      fail(QHIP_INVALID_ARGUMENT, "qhip_snappy_decode: stream " + std::to_string(k) + " lies outside the bytes, or a size is negative or above 2^31 - 1");
+      fail(QHIP_INVALID_ARGUMENT, fn + ": stream " + std::to_string(k) + " lies outside the bytes, or a size is negative or above 2^31 - 1");
     total_out += (uint64_t)dst_sizes[k];
   }
-  if (total_out > (uint64_t)out_bytes) fail(QHIP_INVALID_ARGUMENT, "qhip_snappy_decode: out is smaller than the sum of dst_sizes");
+  if (total_out > (uint64_t)out_bytes) fail(QHIP_INVALID_ARGUMENT, fn + ": out is smaller than the sum of dst_sizes");
   const uint64_t base = ((uint64_t)n_bytes + 15) & ~(uint64_t)15;
   uint64_t area = 0;
   std::vector<qh_pq_unpack> tab;
   for (int64_t k = 0; k < n_streams; ++k) {
     qh_pq_unpack u;
     memset(&u, 0, sizeof u);
-    const int bad = qh_snap_check_sizes(bytes + src_offsets[k], (uint64_t)(src_offsets[k + 1] - src_offsets[k]), (uint64_t)dst_sizes[k], &u.start);
-    status[k] = bad ? QH_PQ_R_SNAPPY_BASE + bad : QH_PQ_OK;
+    const uint64_t len = (uint64_t)(src_offsets[k + 1] - src_offsets[k]);
+    const int bad = zstd ? qh_zstd_check_frame(bytes + src_offsets[k], len, (uint64_t)dst_sizes[k], &u.start)
+                         : qh_snap_check_sizes(bytes + src_offsets[k], len, (uint64_t)dst_sizes[k], &u.start);
+    status[k] = bad ? reason_base + bad : QH_PQ_OK;
     if (bad) continue;
     u.src = (uint64_t)src_offsets[k]; u.src_size = (uint32_t)(src_offsets[k + 1] - src_offsets[k]);
     u.dst = base + area; u.dst_size = (uint32_t)dst_sizes[k];
@@ -278,7 +288,8 @@ void snappy_decode(Ctx* ctx, const uint8_t* bytes, int64_t n_bytes, const int64_
   hipEvent_t ev[2] = {nullptr, nullptr};
   struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int k = 0; k < 2; ++k) if (e[k]) (void)hipEventDestroy(e[k]); } } ev_guard{ev};
   if (ctx->timing) { QHIP_HIP_CHECK(hipEventCreate(&ev[0])); QHIP_HIP_CHECK(hipEventCreate(&ev[1])); QHIP_HIP_CHECK(hipEventRecord(ev[0], ctx->stream)); }
-  launch_pq_unsnap(buf.as<uint8_t>(), base + area, tab_d.as<qh_pq_unpack>(), nt, nullptr, st_d.as<uint32_t>(), ctx->stream);
+  if (zstd) launch_pq_unzstd(buf.as<uint8_t>(), tab_d.as<qh_pq_unpack>(), nt, nullptr, st_d.as<uint32_t>(), ctx->stream);
+  else launch_pq_unsnap(buf.as<uint8_t>(), base + area, tab_d.as<qh_pq_unpack>(), nt, nullptr, st_d.as<uint32_t>(), ctx->stream);
   if (ctx->timing) QHIP_HIP_CHECK(hipEventRecord(ev[1], ctx->stream));
   std::vector<uint8_t> unpacked((size_t)area);
   std::vector<uint32_t> st(nt);
@@ -290,9 +301,17 @@ void snappy_decode(Ctx* ctx, const uint8_t* bytes, int64_t n_bytes, const int64_
   for (int64_t k = 0; k < n_streams; ++k) { out_at[(size_t)k] = at; at += (uint64_t)dst_sizes[k]; }
   for (uint32_t i = 0; i < nt; ++i) {
     const qh_pq_unpack& u = tab[i];
-    status[u.page] = st[i] ? (int32_t)(QH_PQ_R_SNAPPY_BASE + st[i]) : QH_PQ_OK;
+    status[u.page] = st[i] ? (int32_t)(reason_base + st[i]) : QH_PQ_OK;
     if (!st[i] && u.dst_size) memcpy(out + out_at[u.page], unpacked.data() + (u.dst - base), u.dst_size);
   }
+}
+void snappy_decode(Ctx* ctx, const uint8_t* bytes, int64_t n_bytes, const int64_t* src_offsets, const int64_t* dst_sizes, int64_t n_streams, uint8_t* out,
+                   int64_t out_bytes, int32_t* status) {
+  unpack_decode(ctx, false, bytes, n_bytes, src_offsets, dst_sizes, n_streams, out, out_bytes, status);
+}
+void zstd_decode(Ctx* ctx, const uint8_t* bytes, int64_t n_bytes, const int64_t* src_offsets, const int64_t* dst_sizes, int64_t n_streams, uint8_t* out,
+                 int64_t out_bytes, int32_t* status) {
+  unpack_decode(ctx, true, bytes, n_bytes, src_offsets, dst_sizes, n_streams, out, out_bytes, status);
 }
 
 // qhip_parquet_delta_decode: k_pq_delta over raw DELTA_BINARY_PACKED streams. A refused stream is an answer (status), not an error.
@@ -391,6 +410,14 @@ int qhip_snappy_decode(qhip_ctx* ctx, const void* bytes, int64_t n_bytes, const 
   if (n_streams > 0 && (!src_offsets || !dst_sizes || !status)) return QHIP_INVALID_ARGUMENT;
   if (n_streams >= (1 << 24)) return QHIP_INVALID_ARGUMENT;
   return guarded(ctx, [&] { snappy_decode(ctx, (const uint8_t*)bytes, n_bytes, src_offsets, dst_sizes, n_streams, (uint8_t*)out, out_bytes, status); });
+}
+
+int qhip_zstd_decode(qhip_ctx* ctx, const void* bytes, int64_t n_bytes, const int64_t* src_offsets, const int64_t* dst_sizes, int64_t n_streams, void* out,
+                     int64_t out_bytes, int32_t* status) {
+  if (!ctx || n_bytes < 0 || (n_bytes > 0 && !bytes) || n_streams < 0 || out_bytes < 0 || (out_bytes > 0 && !out)) return QHIP_INVALID_ARGUMENT;
+  if (n_streams > 0 && (!src_offsets || !dst_sizes || !status)) return QHIP_INVALID_ARGUMENT;
+  if (n_streams >= (1 << 24)) return QHIP_INVALID_ARGUMENT;
+  return guarded(ctx, [&] { zstd_decode(ctx, (const uint8_t*)bytes, n_bytes, src_offsets, dst_sizes, n_streams, (uint8_t*)out, out_bytes, status); });
 }
 
 }  // extern "C"

@@ -251,6 +251,7 @@ extern "C" {
     pub fn qhip_ctx_parquet_unpack_ms(ctx: *const qhip_ctx, out: *mut f64) -> c_int;
     pub fn qhip_ctx_set_parquet_format(ctx: *mut qhip_ctx, level: i32) -> c_int;
     pub fn qhip_ctx_set_parquet_encodings(ctx: *mut qhip_ctx, set: i32) -> c_int;
+    pub fn qhip_ctx_set_parquet_codecs(ctx: *mut qhip_ctx, set: i32) -> c_int;
     pub fn qhip_ctx_parquet_delta_ms(ctx: *const qhip_ctx, out: *mut f64) -> c_int;
     pub fn qhip_table_to_arrow(
         ctx: *mut qhip_ctx,

@@ -83,6 +83,9 @@ impl HipContext {
         // Parquet files as version-2 writers produce them: data pages V2, RLE Booleans, BYTE_STREAM_SPLIT and the DELTA
         // encodings are decoded on the device too (an independent switch: which codecs is the format level's business)
         unsafe { qhip_ctx_set_parquet_encodings(raw, 2) };
+        // Parquet files as writers that set a codec by hand usually produce them: ZSTD pages are unpacked on the device as well (a
+        // third independent switch: SNAPPY stays with the format level)
+        unsafe { qhip_ctx_set_parquet_codecs(raw, 2) };
         Ok(Arc::new(Self { raw, lock: Mutex::new(()), tables: Mutex::new(HashMap::new()) }))
     }
     pub fn raw(&self) -> *mut qhip_ctx {
