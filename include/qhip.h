@@ -379,7 +379,8 @@ int qhip_ctx_json_pass_ms(const qhip_ctx* ctx, double* out, int32_t n_out);
  * writes by default: their pages cross PCIe compressed and are unpacked on the device; a page whose stream is damaged, or which
  * claims more than 64/3 times its compressed size, needs the host ("Snappy").
  * Needs the host: a compressed projected chunk (level 1: every codec, so write with compression="NONE" or set level 2; level 2:
- * every codec but SNAPPY — zstd, gzip, lz4, brotli; codec set 2, qhip_ctx_set_parquet_codecs below, takes ZSTD), data pages V2 (encoding set 1; qhip_ctx_set_parquet_encodings below), index
+ * every codec but SNAPPY — zstd, gzip, lz4, brotli; codec set 2, qhip_ctx_set_parquet_codecs below, takes ZSTD, and the gzip
+ * switch, qhip_ctx_set_parquet_gzip below, takes GZIP; LZ4, brotli and zlib-wrapped pages stay on the host), data pages V2 (encoding set 1; qhip_ctx_set_parquet_encodings below), index
  * pages, an encrypted footer, a group / list / map field anywhere in the schema, a chunk with file_path, any other encoding
  * (DELTA_*, BYTE_STREAM_SPLIT, RLE values; encoding set 2 decodes these but DELTA_BYTE_ARRAY), BIT_PACKED levels, every other type pair (a zoned Timestamp, Date64, Time, Float16,
  * Decimal256, INT96, LargeUtf8, Binary, dictionary-typed fields), a stored value outside an Int8/Int16/UInt8/UInt16 column's
@@ -391,9 +392,9 @@ int qhip_table_from_parquet(qhip_ctx* ctx, const struct ArrowSchema* schema, con
 /* Device time (ms) of the last qhip_table_from_parquet's five passes — upload, levels, string walk, values, Utf8 — when the
  * context's timing is on (qhip_ctx_set_timing); zeros otherwise. n_out must be 5. */
 int qhip_ctx_parquet_pass_ms(const qhip_ctx* ctx, double* out, int32_t n_out);
-/* Device time (ms) of the unpack passes (format level 2: Snappy pages, codec set 2: ZSTD pages -> the unpack area) of the last
- * qhip_table_from_parquet, or of the last qhip_snappy_decode's or qhip_zstd_decode's kernel, when the context's timing is on; 0
- * otherwise and for a file without Snappy or ZSTD pages. The passes run between "upload" and "levels" and belong to neither of
+/* Device time (ms) of the unpack passes (format level 2: Snappy pages, codec set 2: ZSTD pages, the gzip switch: GZIP pages ->
+ * the unpack area) of the last qhip_table_from_parquet, or of the last qhip_snappy_decode's, qhip_zstd_decode's or
+ * qhip_gzip_decode's kernel, when the context's timing is on; 0 otherwise and for a file without Snappy, ZSTD or GZIP pages. The passes run between "upload" and "levels" and belong to neither of
  * qhip_ctx_parquet_pass_ms's five values. */
 int qhip_ctx_parquet_unpack_ms(const qhip_ctx* ctx, double* out);
 /* The format qhip_table_from_parquet decodes. level 1 (the default): uncompressed chunks only. level 2: also SNAPPY chunks,
@@ -429,6 +430,21 @@ int qhip_ctx_set_parquet_encodings(qhip_ctx* ctx, int32_t set);
  * file without ZSTD chunks launches what set 1 launches. Any other set answers QHIP_INVALID_ARGUMENT and leaves the set as it
  * was. The environment's QHIP_PARQUET_CODECS (1 / 2) is read when the context is created. */
 int qhip_ctx_set_parquet_codecs(qhip_ctx* ctx, int32_t set);
+/* Whether qhip_table_from_parquet unpacks GZIP chunks (Parquet codec 2) on the device: a fourth switch, independent of the
+ * format level, the encoding set and the codec set, none of which it changes. on 0 (the default): a projected GZIP chunk is "a
+ * compressed column chunk" and needs the host. on 1: each page of such a chunk is one gzip member (RFC 1952) around one
+ * DEFLATE stream (RFC 1951), decoded whole by a kernel of its own, one wavefront per page: stored, fixed and dynamic blocks,
+ * the decode tables built in LDS. A file with gzip and Snappy columns needs this switch and level 2, one with gzip and ZSTD
+ * columns this switch and codec set 2, a gzip file with data pages V2 this switch and encoding set 2. The host reads the member
+ * header before anything is reserved and sends to the host path ("Gzip") a page that is not one plain member — a zlib (RFC
+ * 1950) wrapper, another method than 8, a reserved flag, optional fields (FEXTRA, FNAME, FCOMMENT, FHCRC are skipped) that pass
+ * the page — an ISIZE that differs from uncompressed_page_size mod 2^32, and an uncompressed_page_size above 1032 times the
+ * body's bytes, which no DEFLATE stream reaches. The kernel refuses whatever the format forbids and bytes between the final
+ * block and the trailer (a second member). The CRC32 is skipped, not verified, and the 32 KB window is not enforced: a distance
+ * may reach the page's first byte. A file without GZIP chunks launches what it launches with the switch off. Any other value
+ * answers QHIP_INVALID_ARGUMENT and leaves the switch as it was. The environment's QHIP_PARQUET_GZIP (0 / 1) is read when the
+ * context is created. */
+int qhip_ctx_set_parquet_gzip(qhip_ctx* ctx, int32_t on);
 /* Device time (ms) of the delta pass (encoding set 2: DELTA_* pages -> the decoded area) of the last qhip_table_from_parquet, or
  * of the last qhip_parquet_delta_decode's kernel, when the context's timing is on; 0 otherwise and for a file without such
  * pages. The pass runs between "levels" and "string walk" and belongs to neither of qhip_ctx_parquet_pass_ms's five values. */
@@ -456,6 +472,11 @@ int qhip_snappy_decode(qhip_ctx* ctx, const void* bytes, int64_t n_bytes, const 
  * set 2 over raw frames, as a Parquet page holds them. The checks made first are the page walk's (the frame header, the chain of
  * block headers, the declared size against Frame_Content_Size and the blocks' bound); status[k]: 0 or a QH_PQ_R_ZSTD_*. */
 int qhip_zstd_decode(qhip_ctx* ctx, const void* bytes, int64_t n_bytes, const int64_t* src_offsets, const int64_t* dst_sizes,
+                     int64_t n_streams, void* out, int64_t out_bytes, int32_t* status);
+/* The same for the device DEFLATE decoder of the gzip switch over raw gzip members, as a Parquet page holds them. The checks
+ * made first are the page walk's (the member header, ISIZE and the body's bound against the declared size); status[k]: 0 or a
+ * QH_PQ_R_GZIP_*. */
+int qhip_gzip_decode(qhip_ctx* ctx, const void* bytes, int64_t n_bytes, const int64_t* src_offsets, const int64_t* dst_sizes,
                      int64_t n_streams, void* out, int64_t out_bytes, int32_t* status);
 /* Download batch `batch_index` as a struct ArrowArray (+ schema if out_schema != NULL).
  * Buffers are library-owned host memory freed by the release callbacks.

@@ -51,6 +51,8 @@ class Context {
   // BYTE_STREAM_SPLIT, DELTA_BINARY_PACKED and DELTA_LENGTH_BYTE_ARRAY)
   void set_parquet_encodings(int set) const { check(qhip_ctx_set_parquet_encodings(ctx_, set)); }
   void set_parquet_codecs(int set) const { check(qhip_ctx_set_parquet_codecs(ctx_, set)); }
+  // ... and its gzip switch (qhip.h: 0 off, 1 GZIP chunks are inflated on the device), independent of the three above
+  void set_parquet_gzip(int on) const { check(qhip_ctx_set_parquet_gzip(ctx_, on)); }
 
  private:
   qhip_ctx* ctx_ = nullptr;

@@ -316,7 +316,7 @@ struct Ctx {
   float json_pass_ms[5] = {0, 0, 0, 0, 0};
   // ... and of the last qhip_table_from_parquet's (parquet.cpp): upload, levels, string walk, values, Utf8
   float parquet_pass_ms[5] = {0, 0, 0, 0, 0};
-  // ... and of its unpack passes (k_pq_unsnap, k_pq_unzstd, between "upload" and "levels"): 0 for a file without Snappy or ZSTD pages
+  // ... and of its unpack passes (k_pq_unsnap, k_pq_unzstd, k_pq_ungzip, between "upload" and "levels"): 0 for a file without Snappy, ZSTD or GZIP pages
   float parquet_unpack_ms = 0;
   // the device Parquet decoder's format level (parquet.cpp): 1 = uncompressed chunks only, 2 = + SNAPPY chunks;
   // QHIP_PARQUET_FORMAT at context creation, qhip_ctx_set_parquet_format later
@@ -328,6 +328,9 @@ struct Ctx {
   // ... and its codec set, independent of both: 1 = the codecs the format level admits, 2 = + ZSTD chunks (k_pq_unzstd);
   // QHIP_PARQUET_CODECS at context creation, qhip_ctx_set_parquet_codecs later
   int parquet_codecs = 1;
+  // ... and its gzip switch, independent of all three: 1 = + GZIP chunks (k_pq_ungzip); QHIP_PARQUET_GZIP at context creation,
+  // qhip_ctx_set_parquet_gzip later
+  int parquet_gzip = 0;
   // device time of the delta pass (k_pq_delta, between "levels" and "string walk"): 0 for a file without DELTA_* pages
   float parquet_delta_ms = 0;
   // the device CSV decoder's grammar level (csv.cpp): 1 = plain fields only, 2 = + canonical quoted fields, Boolean, Timestamp;

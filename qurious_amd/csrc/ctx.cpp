@@ -353,6 +353,7 @@ int qhip_ctx_create(int device_index, qhip_ctx** out) {
     c->parquet_format = env_int("QHIP_PARQUET_FORMAT", 1) == 2 ? 2 : 1;
     c->parquet_encodings = env_int("QHIP_PARQUET_ENCODINGS", 1) == 2 ? 2 : 1;
     c->parquet_codecs = env_int("QHIP_PARQUET_CODECS", 1) == 2 ? 2 : 1;
+    c->parquet_gzip = env_int("QHIP_PARQUET_GZIP", 0) == 1 ? 1 : 0;
     c->pinned_bytes = 256 * 1024;
     QHIP_HIP_CHECK(hipHostMalloc(&c->pinned, c->pinned_bytes, hipHostMallocDefault));
     memset(&c->stats, 0, sizeof(c->stats));
@@ -438,6 +439,12 @@ int qhip_ctx_set_parquet_encodings(qhip_ctx* ctx, int32_t set) {
 int qhip_ctx_set_parquet_codecs(qhip_ctx* ctx, int32_t set) {
   if (!ctx || set < 1 || set > 2) return QHIP_INVALID_ARGUMENT;
   ctx->parquet_codecs = set;
+  return QHIP_OK;
+}
+
+int qhip_ctx_set_parquet_gzip(qhip_ctx* ctx, int32_t on) {
+  if (!ctx || on < 0 || on > 1) return QHIP_INVALID_ARGUMENT;
+  ctx->parquet_gzip = on;
   return QHIP_OK;
 }
 

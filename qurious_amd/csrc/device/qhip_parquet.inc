@@ -86,7 +86,19 @@ typedef long long pq_i64;
 #define QH_PQ_R_ZSTD_BITS 55       // a backward bit stream that underflows or does not end exactly at its start
 #define QH_PQ_R_ZSTD_OUTPUT 56     // output past uncompressed_page_size, or a frame that ends with output missing
 #define QH_PQ_R_ZSTD_OFFSET 57     // a match offset of 0 or beyond the bytes produced
-#define QH_PQ_R_COUNT 58
+// (the gzip switch, qhip_ctx_set_parquet_gzip: a GZIP page, device/qhip_inflate.inc. QH_PQ_R_GZIP_BASE + QH_INFL_E_*)
+#define QH_PQ_R_GZIP_BASE 57
+#define QH_PQ_R_GZIP_MEMBER 58     // the member header: magic (a zlib wrapper among the rest), CM, a reserved FLG bit, an optional field cut off, no room for a body and the trailer
+#define QH_PQ_R_GZIP_SIZE 59       // ISIZE against uncompressed_page_size mod 2^32, or a size above 1032 x the body's bytes
+#define QH_PQ_R_GZIP_BLOCK 60      // a block header: BTYPE 3, a stored block whose LEN and NLEN do not match
+#define QH_PQ_R_GZIP_LENGTHS 61    // a dynamic block's code lengths: HLIT, HDIST, the code-length code, a repeat with nothing before it or past the count
+#define QH_PQ_R_GZIP_CODE 62       // a literal/length or distance code that is over-subscribed or incomplete, or has no end-of-block code
+#define QH_PQ_R_GZIP_SYMBOL 63     // bits that are no code, literal/length symbol 286 / 287, distance symbol 30 / 31
+#define QH_PQ_R_GZIP_DISTANCE 64   // a distance of 0 or beyond the bytes produced
+#define QH_PQ_R_GZIP_OUTPUT 65     // output past uncompressed_page_size, or a final block that ends with output missing
+#define QH_PQ_R_GZIP_INPUT 66      // the input ends inside a header, a code length, a symbol or a stored block
+#define QH_PQ_R_GZIP_TRAILER 67    // bytes between the final block and the trailer: a second member among the rest
+#define QH_PQ_R_COUNT 68
 
 QH_PQ_HD inline const char* qh_pq_reason_text(unsigned r) {
   switch (r) {
@@ -147,6 +159,16 @@ QH_PQ_HD inline const char* qh_pq_reason_text(unsigned r) {
     case QH_PQ_R_ZSTD_BITS: return "corrupt: a Zstd bit stream that underflows or does not end exactly at its start";
     case QH_PQ_R_ZSTD_OUTPUT: return "corrupt: a Zstd page whose output passes or does not fill uncompressed_page_size";
     case QH_PQ_R_ZSTD_OFFSET: return "corrupt: a Zstd match offset of 0 or beyond the bytes produced";
+    case QH_PQ_R_GZIP_MEMBER: return "a Gzip page whose member header is not one plain gzip member: magic, method, reserved flags, or a header cut off";
+    case QH_PQ_R_GZIP_SIZE: return "corrupt: a Gzip page whose ISIZE or body size does not fit uncompressed_page_size";
+    case QH_PQ_R_GZIP_BLOCK: return "corrupt: a Gzip block header of the reserved type, or a stored block whose lengths do not match";
+    case QH_PQ_R_GZIP_LENGTHS: return "corrupt: Gzip code lengths outside the format's rules";
+    case QH_PQ_R_GZIP_CODE: return "corrupt: a Gzip Huffman code that is over-subscribed, incomplete or without an end-of-block code";
+    case QH_PQ_R_GZIP_SYMBOL: return "corrupt: a Gzip symbol that is no code or outside the alphabet";
+    case QH_PQ_R_GZIP_DISTANCE: return "corrupt: a Gzip match distance of 0 or beyond the bytes produced";
+    case QH_PQ_R_GZIP_OUTPUT: return "corrupt: a Gzip page whose output passes or does not fill uncompressed_page_size";
+    case QH_PQ_R_GZIP_INPUT: return "corrupt: a Gzip page whose input ends inside a block";
+    case QH_PQ_R_GZIP_TRAILER: return "a Gzip page with bytes between its final block and its trailer: a second member, or stray bytes";
     default: return "outside the device's Parquet coverage";
   }
 }
@@ -204,7 +226,8 @@ typedef struct qh_pq_dstream {
 
 // one compressed page (format level 2): k_pq_unsnap turns buffer[src .. src + src_size) into buffer[dst .. dst + dst_size).
 // Codec set 2 keeps the ZSTD pages in a second table of the same entries for k_pq_unzstd: `start` is then where the frame's
-// first block header lies, and dst_size what the frame header says where it says it.
+// first block header lies, and dst_size what the frame header says where it says it. The gzip switch keeps the GZIP pages in
+// a third table for k_pq_ungzip: `start` is where the member's first DEFLATE block lies.
 typedef struct qh_pq_unpack {
   pq_u64 src;         // the compressed payload, in the uploaded chunks
   pq_u64 dst;         // the page's slot in the unpack area, 16-byte aligned

@@ -6,6 +6,7 @@
 // only; the values of a run are spread over the lanes.
 //   k_pq_unsnap   format level 2 only: a Snappy page of the uploaded chunks -> its uncompressed bytes in the unpack area
 //   k_pq_unzstd   codec set 2 only: a ZSTD page of the uploaded chunks -> its uncompressed bytes in the unpack area
+//   k_pq_ungzip   the gzip switch only: a GZIP page of the uploaded chunks -> its uncompressed bytes in the unpack area
 //   k_pq_levels   RLE / bit-packed definition levels -> validity words, the page's non-NULL count, the column's NULL count
 //   k_pq_strings  the length chain of a Utf8 dictionary page or PLAIN data page, staged through LDS -> (length, position)
 //   k_pq_delta    encoding set 2 only: a DELTA_BINARY_PACKED stream -> dense values in the decoded area, or a Utf8 page's entries
@@ -21,6 +22,7 @@
 #include "kernels_parquet.hpp"
 #include "device/qhip_snappy.inc"
 #include "device/qhip_zstd.inc"
+#include "device/qhip_inflate.inc"
 
 namespace qhip {
 
@@ -230,6 +232,28 @@ __global__ __launch_bounds__(64) void k_pq_unzstd(u8* buf, const qh_pq_unpack* _
   if (lane == 0) {
     if (status) status[k] = reason;
     if (reason && err) pq_report(err, u.page, QH_PQ_R_ZSTD_BASE + reason);
+  }
+}
+
+// The gzip switch: one wavefront (a workgroup of its own) unpacks one GZIP page, a gzip member around one DEFLATE stream, from
+// the uploaded chunks into its slot of the unpack area, both in `buf`. The decoder is device/qhip_inflate.inc, which says how:
+// the walk over blocks, code lengths and symbols is wave-uniform; the decode tables of the block's two Huffman codes lie in LDS
+// (7 316 bytes) and are built by the lanes together, lane L counting and placing the symbols of length L, then a symbol per
+// lane filling its cells; decoded literals are gathered a lane each and stored up to 64 at a time; a stored block's bytes and a
+// match are spread over the lanes, a match 64 bytes per step. Bytes that other lanes of the wavefront stored are read back
+// from global memory under the rule k_pq_unsnap rests on, so `buf` is neither const nor __restrict__ here either. The host has
+// checked the member header and ISIZE (qh_gzip_check_member); the walk checks every length, count, code and distance before it
+// is followed. The CRC32 is not verified. A refused page leaves its slot half written.
+__global__ __launch_bounds__(64) void k_pq_ungzip(u8* buf, const qh_pq_unpack* __restrict__ tab, u32 n, u64* err, u32* status) {
+  __shared__ qh_infl_tables T;
+  const u32 k = blockIdx.x;
+  if (k >= n) return;
+  const qh_pq_unpack u = tab[k];
+  const u32 lane = (u32)qh_lane();
+  const u32 reason = qh_inflate_member(buf + u.src, u.src_size, u.start, buf + u.dst, u.dst_size, &T, lane);
+  if (lane == 0) {
+    if (status) status[k] = reason;
+    if (reason && err) pq_report(err, u.page, QH_PQ_R_GZIP_BASE + reason);
   }
 }
 
@@ -507,6 +531,10 @@ void launch_pq_unsnap(uint8_t* buf, uint64_t buf_bytes, const qh_pq_unpack* tab,
 void launch_pq_unzstd(uint8_t* buf, const qh_pq_unpack* tab, uint32_t n, uint64_t* err, uint32_t* status, hipStream_t s) {
   if (!n) return;
   hipLaunchKernelGGL(k_pq_unzstd, dim3(n), dim3(64), 0, s, (u8*)buf, tab, (u32)n, (u64*)err, (u32*)status);
+}
+void launch_pq_ungzip(uint8_t* buf, const qh_pq_unpack* tab, uint32_t n, uint64_t* err, uint32_t* status, hipStream_t s) {
+  if (!n) return;
+  hipLaunchKernelGGL(k_pq_ungzip, dim3(n), dim3(64), 0, s, (u8*)buf, tab, (u32)n, (u64*)err, (u32*)status);
 }
 void launch_pq_strings(const uint8_t* buf, uint64_t buf_bytes, const qh_pq_page* pages, uint32_t npages, const qh_pq_col* cols, const qh_pq_state* state, uint64_t* err,
                        hipStream_t s) {

@@ -10,13 +10,16 @@
 // adds data pages V2, RLE Boolean values, BYTE_STREAM_SPLIT, DELTA_BINARY_PACKED and DELTA_LENGTH_BYTE_ARRAY: a pass in front
 // (k_pq_delta) leaves a delta page's values dense in a decoded area behind the unpack area. Codec set 2
 // (qhip_ctx_set_parquet_codecs), independent of both, adds ZSTD chunks: their pages get slots in the same unpack area and a
-// kernel of their own (k_pq_unzstd, a whole Zstandard frame decoder; the content checksum is not verified). Whatever lies outside makes the whole call answer QHIP_UNSUPPORTED with nothing
+// kernel of their own (k_pq_unzstd, a whole Zstandard frame decoder; the content checksum is not verified). The gzip switch
+// (qhip_ctx_set_parquet_gzip), a fourth independent one, adds GZIP chunks the same way (k_pq_ungzip, an inflate kernel; the
+// CRC32 is not verified). Whatever lies outside makes the whole call answer QHIP_UNSUPPORTED with nothing
 // created, and the caller takes the host path, which then produces every error message.
 //
 // Passes, all on the context's stream:
 //   1 upload        the projected chunks, one behind the other, into one device buffer; the page table and column descriptors
 //  (k_pq_unsnap    level 2, a file with Snappy pages only: one wavefront per page, into the unpack area)
 //  (k_pq_unzstd    codec set 2, a file with ZSTD pages only: one wavefront per page, into the unpack area)
+//  (k_pq_ungzip    the gzip switch, a file with GZIP pages only: one wavefront per page, into the unpack area)
 //   2 k_pq_levels   definition levels -> validity words, non-NULL count per page, NULL count per column
 //  (k_pq_delta     set 2, a file with DELTA_* pages only: one wavefront per page, into the decoded area or the column's entries)
 //   3 k_pq_strings  Utf8: the length chains of dictionary pages and PLAIN data pages -> (length, position) entries
@@ -71,7 +74,7 @@ qhip_table* table_from_parquet(Ctx* ctx, const ArrowSchema* schema, const uint8_
   // ---- footer and page walk (host, one header per page)
   qhip_pq::Plan plan;
   try {
-    plan = qhip_pq::plan_file(bytes, (uint64_t)n_bytes, &names, types, proj, ctx->parquet_format, ctx->parquet_encodings, ctx->parquet_codecs);
+    plan = qhip_pq::plan_file(bytes, (uint64_t)n_bytes, &names, types, proj, ctx->parquet_format, ctx->parquet_encodings, ctx->parquet_codecs, ctx->parquet_gzip);
   } catch (const qhip_pq::PqNeedsHost& e) {
     fail(QHIP_UNSUPPORTED, qhip_pq::needs_host_text(e));
   }
@@ -163,17 +166,22 @@ qhip_table* table_from_parquet(Ctx* ctx, const ArrowSchema* schema, const uint8_
   DevBuf unzstd_d;
   if (nunzstd) unzstd_d.alloc((size_t)nunzstd * sizeof(qh_pq_unpack));
   if (nunzstd) QHIP_HIP_CHECK(hipMemcpyAsync(unzstd_d.ptr, plan.unzstd.data(), (size_t)nunzstd * sizeof(qh_pq_unpack), hipMemcpyHostToDevice, ctx->stream));
+  const uint32_t nungzip = (uint32_t)plan.ungzip.size();
+  DevBuf ungzip_d;
+  if (nungzip) ungzip_d.alloc((size_t)nungzip * sizeof(qh_pq_unpack));
+  if (nungzip) QHIP_HIP_CHECK(hipMemcpyAsync(ungzip_d.ptr, plan.ungzip.data(), (size_t)nungzip * sizeof(qh_pq_unpack), hipMemcpyHostToDevice, ctx->stream));
   const uint32_t ndelta = (uint32_t)plan.delta.size();
   DevBuf delta_d;
   if (ndelta) delta_d.alloc((size_t)ndelta * sizeof(qh_pq_dstream));
   if (ndelta) QHIP_HIP_CHECK(hipMemcpyAsync(delta_d.ptr, plan.delta.data(), (size_t)ndelta * sizeof(qh_pq_dstream), hipMemcpyHostToDevice, ctx->stream));
   mark(1);
 
-  // ---- level 2: the Snappy pages into their slots; codec set 2: the ZSTD pages into theirs
+  // ---- level 2: the Snappy pages into their slots; codec set 2: the ZSTD pages into theirs; the gzip switch: the GZIP pages
   time_mark(ctx, 2);
   if (nunpack) launch_pq_unsnap(file.as<uint8_t>(), buf_bytes, unpack_d.as<qh_pq_unpack>(), nunpack, st_dev + kUnpackWord, nullptr, ctx->stream);
   if (nunzstd) launch_pq_unzstd(file.as<uint8_t>(), unzstd_d.as<qh_pq_unpack>(), nunzstd, st_dev + kUnpackWord, nullptr, ctx->stream);
-  if (nunpack || nunzstd) mark(6);
+  if (nungzip) launch_pq_ungzip(file.as<uint8_t>(), ungzip_d.as<qh_pq_unpack>(), nungzip, st_dev + kUnpackWord, nullptr, ctx->stream);
+  if (nunpack || nunzstd || nungzip) mark(6);
 
   // ---- 2 .. 4: levels, string walk, values
   launch_pq_levels(file.as<uint8_t>(), pages_d.as<qh_pq_page>(), npages, cols_d.as<qh_pq_col>(), state_d.as<qh_pq_state>(), st_dev, st_dev + 1, ctx->stream);
@@ -247,12 +255,15 @@ qhip_table* table_from_parquet(Ctx* ctx, const ArrowSchema* schema, const uint8_
   return t.release();
 }
 
-// qhip_snappy_decode / qhip_zstd_decode: k_pq_unsnap / k_pq_unzstd over raw streams, with the checks the page walk makes of a
-// page's sizes (of a ZSTD page: its frame header and block headers). A refused stream is an answer (status), not an error.
-static void unpack_decode(Ctx* ctx, bool zstd, const uint8_t* bytes, int64_t n_bytes, const int64_t* src_offsets, const int64_t* dst_sizes, int64_t n_streams,
+// qhip_snappy_decode / qhip_zstd_decode / qhip_gzip_decode: k_pq_unsnap / k_pq_unzstd / k_pq_ungzip over raw streams, with the
+// checks the page walk makes of a page's sizes (of a ZSTD page: its frame header and block headers; of a GZIP page: its member
+// header and ISIZE). A refused stream is an answer (status), not an error.
+enum UnpackCodec { kSnappy, kZstd, kGzip };
+static void unpack_decode(Ctx* ctx, UnpackCodec codec, const uint8_t* bytes, int64_t n_bytes, const int64_t* src_offsets, const int64_t* dst_sizes, int64_t n_streams,
                           uint8_t* out, int64_t out_bytes, int32_t* status) {
-  const std::string fn = zstd ? "qhip_zstd_decode" : "qhip_snappy_decode";
-  const int reason_base = zstd ? QH_PQ_R_ZSTD_BASE : QH_PQ_R_SNAPPY_BASE;
+  const bool zstd = codec == kZstd, gz = codec == kGzip;
+  const std::string fn = gz ? "qhip_gzip_decode" : zstd ? "qhip_zstd_decode" : "qhip_snappy_decode";
+  const int reason_base = gz ? QH_PQ_R_GZIP_BASE : zstd ? QH_PQ_R_ZSTD_BASE : QH_PQ_R_SNAPPY_BASE;
   uint64_t total_out = 0;
   for (int64_t k = 0; k < n_streams; ++k) {
     const int64_t a = src_offsets[k], b = src_offsets[k + 1];
@@ -268,8 +279,9 @@ static void unpack_decode(Ctx* ctx, bool zstd, const uint8_t* bytes, int64_t n_b
     qh_pq_unpack u;
     memset(&u, 0, sizeof u);
     const uint64_t len = (uint64_t)(src_offsets[k + 1] - src_offsets[k]);
-    const int bad = zstd ? qh_zstd_check_frame(bytes + src_offsets[k], len, (uint64_t)dst_sizes[k], &u.start)
-                         : qh_snap_check_sizes(bytes + src_offsets[k], len, (uint64_t)dst_sizes[k], &u.start);
+    const int bad = gz     ? qh_gzip_check_member(bytes + src_offsets[k], len, (uint64_t)dst_sizes[k], &u.start)
+                    : zstd ? qh_zstd_check_frame(bytes + src_offsets[k], len, (uint64_t)dst_sizes[k], &u.start)
+                           : qh_snap_check_sizes(bytes + src_offsets[k], len, (uint64_t)dst_sizes[k], &u.start);
     status[k] = bad ? reason_base + bad : QH_PQ_OK;
     if (bad) continue;
     u.src = (uint64_t)src_offsets[k]; u.src_size = (uint32_t)(src_offsets[k + 1] - src_offsets[k]);
@@ -288,7 +300,8 @@ static void unpack_decode(Ctx* ctx, bool zstd, const uint8_t* bytes, int64_t n_b
   hipEvent_t ev[2] = {nullptr, nullptr};
   struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int k = 0; k < 2; ++k) if (e[k]) (void)hipEventDestroy(e[k]); } } ev_guard{ev};
   if (ctx->timing) { QHIP_HIP_CHECK(hipEventCreate(&ev[0])); QHIP_HIP_CHECK(hipEventCreate(&ev[1])); QHIP_HIP_CHECK(hipEventRecord(ev[0], ctx->stream)); }
-  if (zstd) launch_pq_unzstd(buf.as<uint8_t>(), tab_d.as<qh_pq_unpack>(), nt, nullptr, st_d.as<uint32_t>(), ctx->stream);
+  if (gz) launch_pq_ungzip(buf.as<uint8_t>(), tab_d.as<qh_pq_unpack>(), nt, nullptr, st_d.as<uint32_t>(), ctx->stream);
+  else if (zstd) launch_pq_unzstd(buf.as<uint8_t>(), tab_d.as<qh_pq_unpack>(), nt, nullptr, st_d.as<uint32_t>(), ctx->stream);
   else launch_pq_unsnap(buf.as<uint8_t>(), base + area, tab_d.as<qh_pq_unpack>(), nt, nullptr, st_d.as<uint32_t>(), ctx->stream);
   if (ctx->timing) QHIP_HIP_CHECK(hipEventRecord(ev[1], ctx->stream));
   std::vector<uint8_t> unpacked((size_t)area);
@@ -307,11 +320,15 @@ static void unpack_decode(Ctx* ctx, bool zstd, const uint8_t* bytes, int64_t n_b
 }
 void snappy_decode(Ctx* ctx, const uint8_t* bytes, int64_t n_bytes, const int64_t* src_offsets, const int64_t* dst_sizes, int64_t n_streams, uint8_t* out,
                    int64_t out_bytes, int32_t* status) {
-  unpack_decode(ctx, false, bytes, n_bytes, src_offsets, dst_sizes, n_streams, out, out_bytes, status);
+  unpack_decode(ctx, kSnappy, bytes, n_bytes, src_offsets, dst_sizes, n_streams, out, out_bytes, status);
 }
 void zstd_decode(Ctx* ctx, const uint8_t* bytes, int64_t n_bytes, const int64_t* src_offsets, const int64_t* dst_sizes, int64_t n_streams, uint8_t* out,
                  int64_t out_bytes, int32_t* status) {
-  unpack_decode(ctx, true, bytes, n_bytes, src_offsets, dst_sizes, n_streams, out, out_bytes, status);
+  unpack_decode(ctx, kZstd, bytes, n_bytes, src_offsets, dst_sizes, n_streams, out, out_bytes, status);
+}
+void gzip_decode(Ctx* ctx, const uint8_t* bytes, int64_t n_bytes, const int64_t* src_offsets, const int64_t* dst_sizes, int64_t n_streams, uint8_t* out,
+                 int64_t out_bytes, int32_t* status) {
+  unpack_decode(ctx, kGzip, bytes, n_bytes, src_offsets, dst_sizes, n_streams, out, out_bytes, status);
 }
 
 // qhip_parquet_delta_decode: k_pq_delta over raw DELTA_BINARY_PACKED streams. A refused stream is an answer (status), not an error.
@@ -418,6 +435,14 @@ int qhip_zstd_decode(qhip_ctx* ctx, const void* bytes, int64_t n_bytes, const in
   if (n_streams > 0 && (!src_offsets || !dst_sizes || !status)) return QHIP_INVALID_ARGUMENT;
   if (n_streams >= (1 << 24)) return QHIP_INVALID_ARGUMENT;
   return guarded(ctx, [&] { zstd_decode(ctx, (const uint8_t*)bytes, n_bytes, src_offsets, dst_sizes, n_streams, (uint8_t*)out, out_bytes, status); });
+}
+
+int qhip_gzip_decode(qhip_ctx* ctx, const void* bytes, int64_t n_bytes, const int64_t* src_offsets, const int64_t* dst_sizes, int64_t n_streams, void* out,
+                     int64_t out_bytes, int32_t* status) {
+  if (!ctx || n_bytes < 0 || (n_bytes > 0 && !bytes) || n_streams < 0 || out_bytes < 0 || (out_bytes > 0 && !out)) return QHIP_INVALID_ARGUMENT;
+  if (n_streams > 0 && (!src_offsets || !dst_sizes || !status)) return QHIP_INVALID_ARGUMENT;
+  if (n_streams >= (1 << 24)) return QHIP_INVALID_ARGUMENT;
+  return guarded(ctx, [&] { gzip_decode(ctx, (const uint8_t*)bytes, n_bytes, src_offsets, dst_sizes, n_streams, (uint8_t*)out, out_bytes, status); });
 }
 
 }  // extern "C"

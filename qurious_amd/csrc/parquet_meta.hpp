@@ -4,9 +4,11 @@
 // its Arrow type, and the page walk that turns the projected chunks into a page table and, at format level 2, the pages of Snappy
 // chunks into an unpack table with their slots in the unpack area and, at encoding set 2, data pages V2 and the DELTA_* pages into
 // a delta table with their slots in the decoded area and, at codec set 2, the pages of ZSTD chunks into a second unpack table
-// with slots in the same unpack area. Plain C++, no Arrow, no HIP.
+// with slots in the same unpack area and, with the gzip switch on, the pages of GZIP chunks into a third. Plain
+// C++, no Arrow, no HIP.
 // A ZSTD page's frame header and block headers are checked here (qh_zstd_check_frame) before anything is reserved; its content
-// checksum, where it has one, is skipped and not verified.
+// checksum, where it has one, is skipped and not verified. A GZIP page's member header and ISIZE are checked here
+// (qh_gzip_check_member); its CRC32 is skipped and not verified either.
 // Every offset, length and count comes from the file and is checked before it is followed: a violation throws PqNeedsHost.
 #pragma once
 #include <cstdint>
@@ -19,14 +21,19 @@
 #include "device/qhip_snappy.inc"
 #include "device/qhip_delta.inc"
 #include "device/qhip_zstd.inc"
+#include "device/qhip_inflate.inc"
 
 static_assert(QH_PQ_R_SNAPPY_PREAMBLE == QH_PQ_R_SNAPPY_BASE + QH_SNAP_E_PREAMBLE && QH_PQ_R_SNAPPY_OFFSET == QH_PQ_R_SNAPPY_BASE + QH_SNAP_E_OFFSET &&
                   QH_PQ_R_V2_UNCOMPRESSED == QH_PQ_R_SNAPPY_BASE + QH_SNAP_E_COUNT,
               "the Snappy reasons follow the decoder's error codes, the reasons of encoding set 2 follow them");
 
 static_assert(QH_PQ_R_ZSTD_BASE == QH_PQ_R_DELTA_LENGTH && QH_PQ_R_ZSTD_FRAME == QH_PQ_R_ZSTD_BASE + QH_ZSTD_E_FRAME &&
-                  QH_PQ_R_ZSTD_OFFSET == QH_PQ_R_ZSTD_BASE + QH_ZSTD_E_OFFSET && QH_PQ_R_COUNT == QH_PQ_R_ZSTD_BASE + QH_ZSTD_E_COUNT,
+                  QH_PQ_R_ZSTD_OFFSET == QH_PQ_R_ZSTD_BASE + QH_ZSTD_E_OFFSET && QH_PQ_R_GZIP_MEMBER == QH_PQ_R_ZSTD_BASE + QH_ZSTD_E_COUNT,
               "the Zstd reasons follow the reasons of encoding set 2 and the decoder's error codes");
+
+static_assert(QH_PQ_R_GZIP_BASE == QH_PQ_R_ZSTD_OFFSET && QH_PQ_R_GZIP_MEMBER == QH_PQ_R_GZIP_BASE + QH_INFL_E_MEMBER &&
+                  QH_PQ_R_GZIP_TRAILER == QH_PQ_R_GZIP_BASE + QH_INFL_E_TRAILER && QH_PQ_R_COUNT == QH_PQ_R_GZIP_BASE + QH_INFL_E_COUNT,
+              "the Gzip reasons follow the Zstd reasons and the decoder's error codes");
 
 namespace qhip_pq {
 
@@ -129,7 +136,7 @@ enum { PT_BOOLEAN = 0, PT_INT32 = 1, PT_INT64 = 2, PT_INT96 = 3, PT_FLOAT = 4, P
 enum { ENC_PLAIN = 0, ENC_PLAIN_DICTIONARY = 2, ENC_RLE = 3, ENC_BIT_PACKED = 4, ENC_DELTA_BINARY_PACKED = 5, ENC_DELTA_LENGTH_BYTE_ARRAY = 6, ENC_DELTA_BYTE_ARRAY = 7,
        ENC_RLE_DICTIONARY = 8, ENC_BYTE_STREAM_SPLIT = 9 };
 enum { PAGE_DATA = 0, PAGE_INDEX = 1, PAGE_DICTIONARY = 2, PAGE_DATA_V2 = 3 };
-enum { CODEC_UNCOMPRESSED = 0, CODEC_SNAPPY = 1, CODEC_ZSTD = 6 };
+enum { CODEC_UNCOMPRESSED = 0, CODEC_SNAPPY = 1, CODEC_GZIP = 2, CODEC_ZSTD = 6 };
 enum { L_NONE = 0, L_STRING, L_DECIMAL, L_DATE, L_TIMESTAMP, L_INT, L_OTHER };
 
 struct SchemaElem {
@@ -374,13 +381,16 @@ struct Plan {
   // codec set 2: the pages of the ZSTD chunks (k_pq_unzstd), a table of their own with slots in the same unpack area, in the
   // order of the pages. `start`: where the frame's first block header lies. Empty at codec set 1.
   std::vector<qh_pq_unpack> unzstd;
+  // the gzip switch: the pages of the GZIP chunks (k_pq_ungzip), a third table with slots in the same unpack area. `start`:
+  // where the member's first DEFLATE block lies. Empty with the switch off.
+  std::vector<qh_pq_unpack> ungzip;
   // encoding set 2: the DELTA_BINARY_PACKED pages (k_pq_delta). The dense values of one get a 16-byte aligned slot of
   // num_values x width bytes in the decoded area, which lies behind the unpack area (at decoded_base) in the same buffer;
   // DELTA_LENGTH_BYTE_ARRAY lengths become entries of their column and need no slot. has_ext: some page is for k_pq_values_ext.
   std::vector<qh_pq_dstream> delta;
   uint64_t decoded_base = 0, decoded_bytes = 0;
   bool has_ext = false;
-  uint64_t packed_bytes() const { return unpack.empty() && unzstd.empty() ? upload_bytes : unpack_base + unpack_bytes; }
+  uint64_t packed_bytes() const { return unpack.empty() && unzstd.empty() && ungzip.empty() ? upload_bytes : unpack_base + unpack_bytes; }
   uint64_t buffer_bytes() const { return decoded_bytes ? decoded_base + decoded_bytes : packed_bytes(); }
 };
 
@@ -389,9 +399,10 @@ struct Plan {
 // the encoding set (qhip_ctx_set_parquet_encodings); 2 admits data pages V2, RLE Boolean values, BYTE_STREAM_SPLIT,
 // DELTA_BINARY_PACKED and DELTA_LENGTH_BYTE_ARRAY. At set 1 nothing below differs from what it was before the set existed.
 // codecs: the codec set (qhip_ctx_set_parquet_codecs); 2 admits ZSTD chunks, whatever the level, which goes on governing SNAPPY.
-// At set 1 nothing below differs from what it was before the set existed either.
+// At set 1 nothing below differs from what it was before the set existed either. gzip: the gzip switch
+// (qhip_ctx_set_parquet_gzip); 1 admits GZIP chunks, whatever the other three say; at 0 nothing below differs.
 inline Plan plan_file(const uint8_t* file, uint64_t n, const std::vector<std::string>* names, const std::vector<ArrowType>& types, const std::vector<int32_t>& proj,
-                      int level = 1, int encodings = 1, int codecs = 1) {
+                      int level = 1, int encodings = 1, int codecs = 1, int gzip = 0) {
   const bool set2 = encodings >= 2;
   if (n >= 4 && memcmp(file, "PARE", 4) == 0) needs_host(QH_PQ_R_ENCRYPTED);
   if (n >= 4 && memcmp(file + n - 4, "PARE", 4) == 0) needs_host(QH_PQ_R_ENCRYPTED);
@@ -450,7 +461,8 @@ inline Plan plan_file(const uint8_t* file, uint64_t n, const std::vector<std::st
       if (!ch.has_meta || ch.type != f.schema[(size_t)proj[k] + 1].type) needs_host(QH_PQ_R_CORRUPT, G, C);
       const bool snappy = level >= 2 && ch.codec == CODEC_SNAPPY;
       const bool zstd = codecs >= 2 && ch.codec == CODEC_ZSTD;
-      const bool packed = snappy || zstd;
+      const bool gz = gzip >= 1 && ch.codec == CODEC_GZIP;
+      const bool packed = snappy || zstd || gz;
       if (ch.codec != CODEC_UNCOMPRESSED && !packed) needs_host(QH_PQ_R_CODEC, G, C);
       const int64_t start = ch.dict_off > 0 ? ch.dict_off : ch.data_off;
       if (start < 4 || ch.total_compressed < 0 || (uint64_t)start > fstart || (uint64_t)ch.total_compressed > fstart - (uint64_t)start) needs_host(QH_PQ_R_CORRUPT, G, C);
@@ -505,13 +517,14 @@ inline Plan plan_file(const uint8_t* file, uint64_t n, const std::vector<std::st
           if (h.uncompressed < 0 || h.uncompressed > 0x7FFFFFFF) needs_host(QH_PQ_R_CORRUPT, G, C, pageno);
           qh_pq_unpack u;
           memset(&u, 0, sizeof u);
-          const int bad = zstd ? qh_zstd_check_frame(chunk + payload + lev, (uint64_t)h.compressed - lev, (uint64_t)h.uncompressed - lev, &u.start)
+          const int bad = gz   ? qh_gzip_check_member(chunk + payload + lev, (uint64_t)h.compressed - lev, (uint64_t)h.uncompressed - lev, &u.start)
+                          : zstd ? qh_zstd_check_frame(chunk + payload + lev, (uint64_t)h.compressed - lev, (uint64_t)h.uncompressed - lev, &u.start)
                                : qh_snap_check_sizes(chunk + payload + lev, (uint64_t)h.compressed - lev, (uint64_t)h.uncompressed - lev, &u.start);
-          if (bad) needs_host((zstd ? QH_PQ_R_ZSTD_BASE : QH_PQ_R_SNAPPY_BASE) + bad, G, C, pageno);
+          if (bad) needs_host((gz ? QH_PQ_R_GZIP_BASE : zstd ? QH_PQ_R_ZSTD_BASE : QH_PQ_R_SNAPPY_BASE) + bad, G, C, pageno);
           u.src = cbuf + payload + lev; u.src_size = (uint32_t)h.compressed - lev;
           u.dst = plan.unpack_bytes; u.dst_size = (uint32_t)h.uncompressed - lev;
           u.page = (uint32_t)plan.pages.size();
-          (zstd ? plan.unzstd : plan.unpack).push_back(u);
+          (gz ? plan.ungzip : zstd ? plan.unzstd : plan.unpack).push_back(u);
           plan.unpack_bytes += ((uint64_t)u.dst_size + 15) & ~(uint64_t)15;
           pg.pos = u.dst;
           size = u.dst_size;
@@ -573,10 +586,11 @@ inline Plan plan_file(const uint8_t* file, uint64_t n, const std::vector<std::st
     first_row += (uint64_t)g.num_rows;
   }
   // ---- the unpack area begins behind the last uploaded chunk: now its slots have their place in the buffer
-  if (!plan.unpack.empty() || !plan.unzstd.empty()) {
+  if (!plan.unpack.empty() || !plan.unzstd.empty() || !plan.ungzip.empty()) {
     plan.unpack_base = (plan.upload_bytes + 15) & ~(uint64_t)15;
     for (qh_pq_unpack& u : plan.unpack) u.dst += plan.unpack_base;
     for (qh_pq_unpack& u : plan.unzstd) u.dst += plan.unpack_base;
+    for (qh_pq_unpack& u : plan.ungzip) u.dst += plan.unpack_base;
     for (size_t p = 0; p < plan.pages.size(); ++p) {
       if (in_unpack[p] & 1) plan.pages[p].pos += plan.unpack_base;
       if (in_unpack[p] & 2) plan.pages[p].dict_pos += plan.unpack_base;

@@ -252,6 +252,18 @@ extern "C" {
     pub fn qhip_ctx_set_parquet_format(ctx: *mut qhip_ctx, level: i32) -> c_int;
     pub fn qhip_ctx_set_parquet_encodings(ctx: *mut qhip_ctx, set: i32) -> c_int;
     pub fn qhip_ctx_set_parquet_codecs(ctx: *mut qhip_ctx, set: i32) -> c_int;
+    pub fn qhip_ctx_set_parquet_gzip(ctx: *mut qhip_ctx, on: i32) -> c_int;
+    pub fn qhip_gzip_decode(
+        ctx: *mut qhip_ctx,
+        bytes: *const c_void,
+        n_bytes: i64,
+        src_offsets: *const i64,
+        dst_sizes: *const i64,
+        n_streams: i64,
+        out: *mut c_void,
+        out_bytes: i64,
+        status: *mut i32,
+    ) -> c_int;
     pub fn qhip_ctx_parquet_delta_ms(ctx: *const qhip_ctx, out: *mut f64) -> c_int;
     pub fn qhip_table_to_arrow(
         ctx: *mut qhip_ctx,
