@@ -380,7 +380,8 @@ int qhip_ctx_json_pass_ms(const qhip_ctx* ctx, double* out, int32_t n_out);
  * claims more than 64/3 times its compressed size, needs the host ("Snappy").
  * Needs the host: a compressed projected chunk (level 1: every codec, so write with compression="NONE" or set level 2; level 2:
  * every codec but SNAPPY — zstd, gzip, lz4, brotli; codec set 2, qhip_ctx_set_parquet_codecs below, takes ZSTD, and the gzip
- * switch, qhip_ctx_set_parquet_gzip below, takes GZIP; LZ4, brotli and zlib-wrapped pages stay on the host), data pages V2 (encoding set 1; qhip_ctx_set_parquet_encodings below), index
+ * switch, qhip_ctx_set_parquet_gzip below, takes GZIP, and the lz4 switch, qhip_ctx_set_parquet_lz4 below, LZ4_RAW and the legacy
+ * LZ4 id; brotli and zlib-wrapped pages stay on the host), data pages V2 (encoding set 1; qhip_ctx_set_parquet_encodings below), index
  * pages, an encrypted footer, a group / list / map field anywhere in the schema, a chunk with file_path, any other encoding
  * (DELTA_*, BYTE_STREAM_SPLIT, RLE values; encoding set 2 decodes these but DELTA_BYTE_ARRAY), BIT_PACKED levels, every other type pair (a zoned Timestamp, Date64, Time, Float16,
  * Decimal256, INT96, LargeUtf8, Binary, dictionary-typed fields), a stored value outside an Int8/Int16/UInt8/UInt16 column's
@@ -392,9 +393,10 @@ int qhip_table_from_parquet(qhip_ctx* ctx, const struct ArrowSchema* schema, con
 /* Device time (ms) of the last qhip_table_from_parquet's five passes — upload, levels, string walk, values, Utf8 — when the
  * context's timing is on (qhip_ctx_set_timing); zeros otherwise. n_out must be 5. */
 int qhip_ctx_parquet_pass_ms(const qhip_ctx* ctx, double* out, int32_t n_out);
-/* Device time (ms) of the unpack passes (format level 2: Snappy pages, codec set 2: ZSTD pages, the gzip switch: GZIP pages ->
- * the unpack area) of the last qhip_table_from_parquet, or of the last qhip_snappy_decode's, qhip_zstd_decode's or
- * qhip_gzip_decode's kernel, when the context's timing is on; 0 otherwise and for a file without Snappy, ZSTD or GZIP pages. The passes run between "upload" and "levels" and belong to neither of
+/* Device time (ms) of the unpack passes (format level 2: Snappy pages, codec set 2: ZSTD pages, the gzip switch: GZIP pages,
+ * the lz4 switch: LZ4 pages -> the unpack area) of the last qhip_table_from_parquet, or of the last qhip_snappy_decode's,
+ * qhip_zstd_decode's, qhip_gzip_decode's or qhip_lz4_decode's kernel, when the context's timing is on; 0 otherwise and for a
+ * file without Snappy, ZSTD, GZIP or LZ4 pages. The passes run between "upload" and "levels" and belong to neither of
  * qhip_ctx_parquet_pass_ms's five values. */
 int qhip_ctx_parquet_unpack_ms(const qhip_ctx* ctx, double* out);
 /* The format qhip_table_from_parquet decodes. level 1 (the default): uncompressed chunks only. level 2: also SNAPPY chunks,
@@ -445,6 +447,24 @@ int qhip_ctx_set_parquet_codecs(qhip_ctx* ctx, int32_t set);
  * answers QHIP_INVALID_ARGUMENT and leaves the switch as it was. The environment's QHIP_PARQUET_GZIP (0 / 1) is read when the
  * context is created. */
 int qhip_ctx_set_parquet_gzip(qhip_ctx* ctx, int32_t on);
+/* Whether qhip_table_from_parquet unpacks LZ4 chunks on the device: a fifth switch, independent of the format level, the
+ * encoding set, the codec set and the gzip switch, none of which it changes. on 0 (the default): a projected LZ4 chunk is "a
+ * compressed column chunk" and needs the host. on 1: both of Parquet's LZ4 codecs are taken. LZ4_RAW (codec 7, what pyarrow's
+ * compression="lz4" writes): each page is one bare LZ4 block, decoded by a kernel of its own, one wavefront per block. The
+ * legacy LZ4 id (codec 5): Hadoop writers put frames of BE32 uncompressed size, BE32 compressed size, block around the blocks,
+ * old Arrow writers wrote one bare block. Arrow's reader decides between the two by decompressing: it tries the frames and
+ * falls back to a bare block. The page walk here decides by arithmetic on what the host sees without decompressing: where one
+ * frame or more tile the page exactly and their uncompressed sizes add up to uncompressed_page_size, the page is framed and
+ * each frame is decoded as a block of its own into its slice of the page; otherwise the page is one bare block. The device
+ * decode is the judge of a framing chosen wrongly: a bare block whose first bytes happen to tile is refused as the frames it is
+ * not, and the page takes the host path ("LZ4") like any damaged page; there is never a wrong result. An LZ4 file with Snappy
+ * columns needs this switch and level 2, one with data pages V2 this switch and encoding set 2. Before anything is reserved the
+ * host refuses a block that claims more than 255 times its bytes, which no LZ4 block reaches. The kernel checks every length
+ * and offset before it is followed and requires that input and output end together behind a literal run; the encoder-side
+ * end-of-block restrictions (the last 5 bytes are literals, the last match begins 12 bytes before the end) are not enforced. A
+ * file without LZ4 chunks launches what it launches with the switch off. Any other value answers QHIP_INVALID_ARGUMENT and
+ * leaves the switch as it was. The environment's QHIP_PARQUET_LZ4 (0 / 1) is read when the context is created. */
+int qhip_ctx_set_parquet_lz4(qhip_ctx* ctx, int32_t on);
 /* Device time (ms) of the delta pass (encoding set 2: DELTA_* pages -> the decoded area) of the last qhip_table_from_parquet, or
  * of the last qhip_parquet_delta_decode's kernel, when the context's timing is on; 0 otherwise and for a file without such
  * pages. The pass runs between "levels" and "string walk" and belongs to neither of qhip_ctx_parquet_pass_ms's five values. */
@@ -478,6 +498,10 @@ int qhip_zstd_decode(qhip_ctx* ctx, const void* bytes, int64_t n_bytes, const in
  * QH_PQ_R_GZIP_*. */
 int qhip_gzip_decode(qhip_ctx* ctx, const void* bytes, int64_t n_bytes, const int64_t* src_offsets, const int64_t* dst_sizes,
                      int64_t n_streams, void* out, int64_t out_bytes, int32_t* status);
+/* The same for the device LZ4 decoder of the lz4 switch over bare LZ4 blocks, as an LZ4_RAW page holds one. The check made
+ * first is the page walk's (the declared size against 255 times the block's bytes); status[k]: 0 or a QH_PQ_R_LZ4_*. */
+int qhip_lz4_decode(qhip_ctx* ctx, const void* bytes, int64_t n_bytes, const int64_t* src_offsets, const int64_t* dst_sizes,
+                    int64_t n_streams, void* out, int64_t out_bytes, int32_t* status);
 /* Download batch `batch_index` as a struct ArrowArray (+ schema if out_schema != NULL).
  * Buffers are library-owned host memory freed by the release callbacks.
  * batch_index == -1: every row of the table as ONE array — a caller facing thousands of small batches (the reference's

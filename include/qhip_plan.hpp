@@ -53,6 +53,8 @@ class Context {
   void set_parquet_codecs(int set) const { check(qhip_ctx_set_parquet_codecs(ctx_, set)); }
   // ... and its gzip switch (qhip.h: 0 off, 1 GZIP chunks are inflated on the device), independent of the three above
   void set_parquet_gzip(int on) const { check(qhip_ctx_set_parquet_gzip(ctx_, on)); }
+  // ... and its lz4 switch (qhip.h: 0 off, 1 LZ4_RAW and legacy LZ4 chunks are unpacked on the device), independent of the four above
+  void set_parquet_lz4(int on) const { check(qhip_ctx_set_parquet_lz4(ctx_, on)); }
 
  private:
   qhip_ctx* ctx_ = nullptr;

@@ -162,6 +162,8 @@ def load_library() -> C.CDLL:
             "qhip_zstd_decode": (C.c_int, [vp, vp, i64, P(i64), P(i64), i64, vp, i64, P(i32)]),
             "qhip_ctx_set_parquet_gzip": (C.c_int, [vp, i32]),
             "qhip_gzip_decode": (C.c_int, [vp, vp, i64, P(i64), P(i64), i64, vp, i64, P(i32)]),
+            "qhip_ctx_set_parquet_lz4": (C.c_int, [vp, i32]),
+            "qhip_lz4_decode": (C.c_int, [vp, vp, i64, P(i64), P(i64), i64, vp, i64, P(i32)]),
             "qhip_ctx_parquet_delta_ms": (C.c_int, [vp, P(C.c_double)]),
             "qhip_parquet_delta_decode": (C.c_int, [vp, vp, i64, P(i64), P(i32), P(i64), i64, vp, i64, P(i64), P(i32)]),
             "qhip_table_to_arrow": (C.c_int, [vp, vp, i64, vp, vp]),
@@ -329,9 +331,16 @@ class Context:
     def set_parquet_gzip(self, on: int):
         """The device Parquet decoder's gzip switch, independent of the format level, the encoding set and the codec set: 0 (the
         default) a GZIP chunk takes the host path; 1 GZIP chunks are unpacked on the device, each page a gzip member inflated
-        by a kernel of its own (the CRC32 is not verified). LZ4, brotli and zlib-wrapped pages stay on the host.
-        QHIP_PARQUET_GZIP sets it when the context is made."""
+        by a kernel of its own (the CRC32 is not verified). Brotli and zlib-wrapped pages stay on the host; LZ4 has a switch of
+        its own. QHIP_PARQUET_GZIP sets it when the context is made."""
         self.check(self.lib.qhip_ctx_set_parquet_gzip(self.handle, int(on)))
+
+    def set_parquet_lz4(self, on: int):
+        """The device Parquet decoder's lz4 switch, independent of the format level, the encoding set, the codec set and the gzip
+        switch: 0 (the default) an LZ4 chunk takes the host path; 1 LZ4_RAW chunks (what `compression="lz4"` writes) and chunks
+        of the legacy LZ4 id (Hadoop's length frames where they tile the page, one bare block otherwise) are unpacked on the
+        device, one wavefront per block. QHIP_PARQUET_LZ4 sets it when the context is made."""
+        self.check(self.lib.qhip_ctx_set_parquet_lz4(self.handle, int(on)))
 
     def parquet_delta_ms(self) -> float:
         """Device time (ms) of the delta pass (k_pq_delta, encoding set 2) of the last device Parquet decode, or of the last
@@ -382,6 +391,13 @@ class Context:
         statuses): statuses[k] is 0 or the needs-host reason (QH_PQ_R_GZIP_*) for which member k was refused, outputs[k] its
         bytes (None when refused)."""
         return self._unpack_decode(self.lib.qhip_gzip_decode, streams, dst_sizes)
+
+    def lz4_decode(self, streams: Sequence[bytes], dst_sizes: Sequence[int]):
+        """A testing and measurement aid (qhip_lz4_decode): bare LZ4 blocks through the device decoder of the lz4 switch, one
+        wavefront each, in one call. `dst_sizes[k]`: the uncompressed size declared for block k. Returns (outputs, statuses):
+        statuses[k] is 0 or the needs-host reason (QH_PQ_R_LZ4_*) for which block k was refused, outputs[k] its bytes (None
+        when refused)."""
+        return self._unpack_decode(self.lib.qhip_lz4_decode, streams, dst_sizes)
 
     def snappy_decode(self, streams: Sequence[bytes], dst_sizes: Sequence[int]):
         """A testing and measurement aid (qhip_snappy_decode): raw Snappy streams through the device decoder of format level 2,

@@ -316,7 +316,7 @@ struct Ctx {
   float json_pass_ms[5] = {0, 0, 0, 0, 0};
   // ... and of the last qhip_table_from_parquet's (parquet.cpp): upload, levels, string walk, values, Utf8
   float parquet_pass_ms[5] = {0, 0, 0, 0, 0};
-  // ... and of its unpack passes (k_pq_unsnap, k_pq_unzstd, k_pq_ungzip, between "upload" and "levels"): 0 for a file without Snappy, ZSTD or GZIP pages
+  // ... and of its unpack passes (k_pq_unsnap, k_pq_unzstd, k_pq_ungzip, k_pq_unlz4, between "upload" and "levels"): 0 for a file without Snappy, ZSTD, GZIP or LZ4 pages
   float parquet_unpack_ms = 0;
   // the device Parquet decoder's format level (parquet.cpp): 1 = uncompressed chunks only, 2 = + SNAPPY chunks;
   // QHIP_PARQUET_FORMAT at context creation, qhip_ctx_set_parquet_format later
@@ -331,6 +331,9 @@ struct Ctx {
   // ... and its gzip switch, independent of all three: 1 = + GZIP chunks (k_pq_ungzip); QHIP_PARQUET_GZIP at context creation,
   // qhip_ctx_set_parquet_gzip later
   int parquet_gzip = 0;
+  // ... and its lz4 switch, independent of all four: 1 = + LZ4_RAW and legacy LZ4 chunks (k_pq_unlz4); QHIP_PARQUET_LZ4 at
+  // context creation, qhip_ctx_set_parquet_lz4 later
+  int parquet_lz4 = 0;
   // device time of the delta pass (k_pq_delta, between "levels" and "string walk"): 0 for a file without DELTA_* pages
   float parquet_delta_ms = 0;
   // the device CSV decoder's grammar level (csv.cpp): 1 = plain fields only, 2 = + canonical quoted fields, Boolean, Timestamp;

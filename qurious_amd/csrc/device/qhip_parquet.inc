@@ -98,7 +98,16 @@ typedef long long pq_i64;
 #define QH_PQ_R_GZIP_OUTPUT 65     // output past uncompressed_page_size, or a final block that ends with output missing
 #define QH_PQ_R_GZIP_INPUT 66      // the input ends inside a header, a code length, a symbol or a stored block
 #define QH_PQ_R_GZIP_TRAILER 67    // bytes between the final block and the trailer: a second member among the rest
-#define QH_PQ_R_COUNT 68
+// (the lz4 switch, qhip_ctx_set_parquet_lz4: an LZ4_RAW or legacy LZ4 page, device/qhip_lz4.inc. QH_PQ_R_LZ4_BASE + QH_LZ4_E_*)
+#define QH_PQ_R_LZ4_BASE 67
+#define QH_PQ_R_LZ4_SIZE 68        // a size above 255 x the block's bytes
+#define QH_PQ_R_LZ4_FRAME 69       // Hadoop framing: the frames tile the page, but one has no bytes for the output it declares
+#define QH_PQ_R_LZ4_CUT 70         // the input ends inside a length's extension or an offset
+#define QH_PQ_R_LZ4_LITERAL 71     // a literal run past the input
+#define QH_PQ_R_LZ4_OUTPUT 72      // a literal run or a match past uncompressed_page_size
+#define QH_PQ_R_LZ4_OFFSET 73      // a match offset of 0 or beyond the bytes produced
+#define QH_PQ_R_LZ4_END 74         // input left behind a full output; input that ends with output missing, or behind a match
+#define QH_PQ_R_COUNT 75
 
 QH_PQ_HD inline const char* qh_pq_reason_text(unsigned r) {
   switch (r) {
@@ -169,6 +178,13 @@ QH_PQ_HD inline const char* qh_pq_reason_text(unsigned r) {
     case QH_PQ_R_GZIP_OUTPUT: return "corrupt: a Gzip page whose output passes or does not fill uncompressed_page_size";
     case QH_PQ_R_GZIP_INPUT: return "corrupt: a Gzip page whose input ends inside a block";
     case QH_PQ_R_GZIP_TRAILER: return "a Gzip page with bytes between its final block and its trailer: a second member, or stray bytes";
+    case QH_PQ_R_LZ4_SIZE: return "corrupt: an LZ4 page whose size exceeds 255 times its compressed bytes";
+    case QH_PQ_R_LZ4_FRAME: return "corrupt: an LZ4 page whose Hadoop frames tile it, one of them without bytes for the output it declares";
+    case QH_PQ_R_LZ4_CUT: return "corrupt: an LZ4 page whose input ends inside a length or an offset";
+    case QH_PQ_R_LZ4_LITERAL: return "corrupt: an LZ4 literal run past the input";
+    case QH_PQ_R_LZ4_OUTPUT: return "corrupt: an LZ4 literal run or match past uncompressed_page_size";
+    case QH_PQ_R_LZ4_OFFSET: return "corrupt: an LZ4 match offset of 0 or beyond the bytes produced";
+    case QH_PQ_R_LZ4_END: return "corrupt: an LZ4 page whose input and output do not end together behind a literal run";
     default: return "outside the device's Parquet coverage";
   }
 }
@@ -227,7 +243,9 @@ typedef struct qh_pq_dstream {
 // one compressed page (format level 2): k_pq_unsnap turns buffer[src .. src + src_size) into buffer[dst .. dst + dst_size).
 // Codec set 2 keeps the ZSTD pages in a second table of the same entries for k_pq_unzstd: `start` is then where the frame's
 // first block header lies, and dst_size what the frame header says where it says it. The gzip switch keeps the GZIP pages in
-// a third table for k_pq_ungzip: `start` is where the member's first DEFLATE block lies.
+// a third table for k_pq_ungzip: `start` is where the member's first DEFLATE block lies. The lz4 switch keeps the LZ4 pages in
+// a fourth for k_pq_unlz4, one entry per bare block: a page in Hadoop's framing has an entry per frame, each with its own source
+// range and its own slice of the page's slot; `start` is 0.
 typedef struct qh_pq_unpack {
   pq_u64 src;         // the compressed payload, in the uploaded chunks
   pq_u64 dst;         // the page's slot in the unpack area, 16-byte aligned

@@ -7,6 +7,7 @@
 //   k_pq_unsnap   format level 2 only: a Snappy page of the uploaded chunks -> its uncompressed bytes in the unpack area
 //   k_pq_unzstd   codec set 2 only: a ZSTD page of the uploaded chunks -> its uncompressed bytes in the unpack area
 //   k_pq_ungzip   the gzip switch only: a GZIP page of the uploaded chunks -> its uncompressed bytes in the unpack area
+//   k_pq_unlz4    the lz4 switch only: an LZ4 block of the uploaded chunks -> its uncompressed bytes in the unpack area
 //   k_pq_levels   RLE / bit-packed definition levels -> validity words, the page's non-NULL count, the column's NULL count
 //   k_pq_strings  the length chain of a Utf8 dictionary page or PLAIN data page, staged through LDS -> (length, position)
 //   k_pq_delta    encoding set 2 only: a DELTA_BINARY_PACKED stream -> dense values in the decoded area, or a Utf8 page's entries
@@ -23,6 +24,7 @@
 #include "device/qhip_snappy.inc"
 #include "device/qhip_zstd.inc"
 #include "device/qhip_inflate.inc"
+#include "device/qhip_lz4.inc"
 
 namespace qhip {
 
@@ -254,6 +256,30 @@ __global__ __launch_bounds__(64) void k_pq_ungzip(u8* buf, const qh_pq_unpack* _
   if (lane == 0) {
     if (status) status[k] = reason;
     if (reason && err) pq_report(err, u.page, QH_PQ_R_GZIP_BASE + reason);
+  }
+}
+
+// The lz4 switch: one wavefront (a workgroup of its own) unpacks one bare LZ4 block — an LZ4_RAW page, a legacy LZ4 page, or one
+// frame of a legacy page in Hadoop's framing, which the host has split — from the uploaded chunks into its slot, or its slice
+// of the page's slot, in the unpack area, both in `buf`. The decoder is device/qhip_lz4.inc, which says how: k_pq_unsnap's
+// sibling. The walk over the sequences is wave-uniform and, each byte it reads declared uniform, scalar; token, extension and
+// offset bytes come from a 1 KB tile of the input staged in LDS, and a literal run that lies inside the tile is taken from
+// there; literals and match bytes are spread over the lanes, four loads in flight, a match of any length in 64-byte steps under
+// qh_snap_copy_src's modulo rule. Bytes that other lanes of the wavefront stored are read back from global memory under the
+// rule k_pq_unsnap rests on, with its wavefront-scope fence per sequence, so `buf` is neither const nor __restrict__ here
+// either. The host has checked the 255x bound (qh_lz4_check_sizes); the walk checks every length and offset before it is
+// followed. A refused block leaves its slot half written.
+static_assert(QH_LZ4_TILE == kPqTile, "the LZ4 decoder's tile is the one the other walks stage their input in");
+__global__ __launch_bounds__(64) void k_pq_unlz4(u8* buf, const qh_pq_unpack* __restrict__ tab, u32 n, u64* err, u32* status) {
+  __shared__ __attribute__((aligned(16))) u8 tile[kPqTile];
+  const u32 k = blockIdx.x;
+  if (k >= n) return;
+  const qh_pq_unpack u = tab[k];
+  const u32 lane = (u32)qh_lane();
+  const u32 reason = qh_lz4_block(buf + u.src, u.src_size, buf + u.dst, u.dst_size, tile, lane);
+  if (lane == 0) {
+    if (status) status[k] = reason;
+    if (reason && err) pq_report(err, u.page, QH_PQ_R_LZ4_BASE + reason);
   }
 }
 
@@ -535,6 +561,10 @@ void launch_pq_unzstd(uint8_t* buf, const qh_pq_unpack* tab, uint32_t n, uint64_
 void launch_pq_ungzip(uint8_t* buf, const qh_pq_unpack* tab, uint32_t n, uint64_t* err, uint32_t* status, hipStream_t s) {
   if (!n) return;
   hipLaunchKernelGGL(k_pq_ungzip, dim3(n), dim3(64), 0, s, (u8*)buf, tab, (u32)n, (u64*)err, (u32*)status);
+}
+void launch_pq_unlz4(uint8_t* buf, const qh_pq_unpack* tab, uint32_t n, uint64_t* err, uint32_t* status, hipStream_t s) {
+  if (!n) return;
+  hipLaunchKernelGGL(k_pq_unlz4, dim3(n), dim3(64), 0, s, (u8*)buf, tab, (u32)n, (u64*)err, (u32*)status);
 }
 void launch_pq_strings(const uint8_t* buf, uint64_t buf_bytes, const qh_pq_page* pages, uint32_t npages, const qh_pq_col* cols, const qh_pq_state* state, uint64_t* err,
                        hipStream_t s) {

@@ -27,6 +27,8 @@ void launch_pq_unsnap(uint8_t* buf, uint64_t buf_bytes, const qh_pq_unpack* tab,
 void launch_pq_unzstd(uint8_t* buf, const qh_pq_unpack* tab, uint32_t n, uint64_t* err, uint32_t* status, hipStream_t s);
 // the gzip switch: one wavefront per GZIP page of `tab` (k_pq_ungzip); err / status as for launch_pq_unsnap
 void launch_pq_ungzip(uint8_t* buf, const qh_pq_unpack* tab, uint32_t n, uint64_t* err, uint32_t* status, hipStream_t s);
+// the lz4 switch: one wavefront per bare LZ4 block of `tab` (k_pq_unlz4); err / status as for launch_pq_unsnap
+void launch_pq_unlz4(uint8_t* buf, const qh_pq_unpack* tab, uint32_t n, uint64_t* err, uint32_t* status, hipStream_t s);
 // definition levels -> validity words (zeroed before), per page its non-NULL count and where its values begin, per column its
 // NULL count. err: the smallest (page << 8 | reason), ~0 when none.
 void launch_pq_levels(const uint8_t* buf, const qh_pq_page* pages, uint32_t npages, const qh_pq_col* cols, qh_pq_state* state, uint64_t* err, uint64_t* null_counts,

@@ -12,7 +12,8 @@
 // (qhip_ctx_set_parquet_codecs), independent of both, adds ZSTD chunks: their pages get slots in the same unpack area and a
 // kernel of their own (k_pq_unzstd, a whole Zstandard frame decoder; the content checksum is not verified). The gzip switch
 // (qhip_ctx_set_parquet_gzip), a fourth independent one, adds GZIP chunks the same way (k_pq_ungzip, an inflate kernel; the
-// CRC32 is not verified). Whatever lies outside makes the whole call answer QHIP_UNSUPPORTED with nothing
+// CRC32 is not verified). The lz4 switch (qhip_ctx_set_parquet_lz4), a fifth, adds LZ4_RAW and legacy LZ4 chunks (k_pq_unlz4,
+// one wavefront per bare block; Hadoop's frames are split on the host). Whatever lies outside makes the whole call answer QHIP_UNSUPPORTED with nothing
 // created, and the caller takes the host path, which then produces every error message.
 //
 // Passes, all on the context's stream:
@@ -20,6 +21,7 @@
 //  (k_pq_unsnap    level 2, a file with Snappy pages only: one wavefront per page, into the unpack area)
 //  (k_pq_unzstd    codec set 2, a file with ZSTD pages only: one wavefront per page, into the unpack area)
 //  (k_pq_ungzip    the gzip switch, a file with GZIP pages only: one wavefront per page, into the unpack area)
+//  (k_pq_unlz4     the lz4 switch, a file with LZ4 pages only: one wavefront per block, into the unpack area)
 //   2 k_pq_levels   definition levels -> validity words, non-NULL count per page, NULL count per column
 //  (k_pq_delta     set 2, a file with DELTA_* pages only: one wavefront per page, into the decoded area or the column's entries)
 //   3 k_pq_strings  Utf8: the length chains of dictionary pages and PLAIN data pages -> (length, position) entries
@@ -74,7 +76,7 @@ qhip_table* table_from_parquet(Ctx* ctx, const ArrowSchema* schema, const uint8_
   // ---- footer and page walk (host, one header per page)
   qhip_pq::Plan plan;
   try {
-    plan = qhip_pq::plan_file(bytes, (uint64_t)n_bytes, &names, types, proj, ctx->parquet_format, ctx->parquet_encodings, ctx->parquet_codecs, ctx->parquet_gzip);
+    plan = qhip_pq::plan_file(bytes, (uint64_t)n_bytes, &names, types, proj, ctx->parquet_format, ctx->parquet_encodings, ctx->parquet_codecs, ctx->parquet_gzip, ctx->parquet_lz4);
   } catch (const qhip_pq::PqNeedsHost& e) {
     fail(QHIP_UNSUPPORTED, qhip_pq::needs_host_text(e));
   }
@@ -170,18 +172,24 @@ qhip_table* table_from_parquet(Ctx* ctx, const ArrowSchema* schema, const uint8_
   DevBuf ungzip_d;
   if (nungzip) ungzip_d.alloc((size_t)nungzip * sizeof(qh_pq_unpack));
   if (nungzip) QHIP_HIP_CHECK(hipMemcpyAsync(ungzip_d.ptr, plan.ungzip.data(), (size_t)nungzip * sizeof(qh_pq_unpack), hipMemcpyHostToDevice, ctx->stream));
+  const uint32_t nunlz4 = (uint32_t)plan.unlz4.size();
+  DevBuf unlz4_d;
+  if (nunlz4) unlz4_d.alloc((size_t)nunlz4 * sizeof(qh_pq_unpack));
+  if (nunlz4) QHIP_HIP_CHECK(hipMemcpyAsync(unlz4_d.ptr, plan.unlz4.data(), (size_t)nunlz4 * sizeof(qh_pq_unpack), hipMemcpyHostToDevice, ctx->stream));
   const uint32_t ndelta = (uint32_t)plan.delta.size();
   DevBuf delta_d;
   if (ndelta) delta_d.alloc((size_t)ndelta * sizeof(qh_pq_dstream));
   if (ndelta) QHIP_HIP_CHECK(hipMemcpyAsync(delta_d.ptr, plan.delta.data(), (size_t)ndelta * sizeof(qh_pq_dstream), hipMemcpyHostToDevice, ctx->stream));
   mark(1);
 
-  // ---- level 2: the Snappy pages into their slots; codec set 2: the ZSTD pages into theirs; the gzip switch: the GZIP pages
+  // ---- level 2: the Snappy pages into their slots; codec set 2: the ZSTD pages into theirs; the gzip switch: the GZIP pages; the lz4
+  // switch: the LZ4 blocks
   time_mark(ctx, 2);
   if (nunpack) launch_pq_unsnap(file.as<uint8_t>(), buf_bytes, unpack_d.as<qh_pq_unpack>(), nunpack, st_dev + kUnpackWord, nullptr, ctx->stream);
   if (nunzstd) launch_pq_unzstd(file.as<uint8_t>(), unzstd_d.as<qh_pq_unpack>(), nunzstd, st_dev + kUnpackWord, nullptr, ctx->stream);
   if (nungzip) launch_pq_ungzip(file.as<uint8_t>(), ungzip_d.as<qh_pq_unpack>(), nungzip, st_dev + kUnpackWord, nullptr, ctx->stream);
-  if (nunpack || nunzstd || nungzip) mark(6);
+  if (nunlz4) launch_pq_unlz4(file.as<uint8_t>(), unlz4_d.as<qh_pq_unpack>(), nunlz4, st_dev + kUnpackWord, nullptr, ctx->stream);
+  if (nunpack || nunzstd || nungzip || nunlz4) mark(6);
 
   // ---- 2 .. 4: levels, string walk, values
   launch_pq_levels(file.as<uint8_t>(), pages_d.as<qh_pq_page>(), npages, cols_d.as<qh_pq_col>(), state_d.as<qh_pq_state>(), st_dev, st_dev + 1, ctx->stream);
@@ -255,15 +263,16 @@ qhip_table* table_from_parquet(Ctx* ctx, const ArrowSchema* schema, const uint8_
   return t.release();
 }
 
-// qhip_snappy_decode / qhip_zstd_decode / qhip_gzip_decode: k_pq_unsnap / k_pq_unzstd / k_pq_ungzip over raw streams, with the
-// checks the page walk makes of a page's sizes (of a ZSTD page: its frame header and block headers; of a GZIP page: its member
-// header and ISIZE). A refused stream is an answer (status), not an error.
-enum UnpackCodec { kSnappy, kZstd, kGzip };
+// qhip_snappy_decode / qhip_zstd_decode / qhip_gzip_decode / qhip_lz4_decode: k_pq_unsnap / k_pq_unzstd / k_pq_ungzip /
+// k_pq_unlz4 over raw streams, with the checks the page walk makes of a page's sizes (of a ZSTD page: its frame header and block
+// headers; of a GZIP page: its member header and ISIZE; of an LZ4 block: the 255x bound). A refused stream is an answer (status),
+// not an error.
+enum UnpackCodec { kSnappy, kZstd, kGzip, kLz4 };
 static void unpack_decode(Ctx* ctx, UnpackCodec codec, const uint8_t* bytes, int64_t n_bytes, const int64_t* src_offsets, const int64_t* dst_sizes, int64_t n_streams,
                           uint8_t* out, int64_t out_bytes, int32_t* status) {
-  const bool zstd = codec == kZstd, gz = codec == kGzip;
-  const std::string fn = gz ? "qhip_gzip_decode" : zstd ? "qhip_zstd_decode" : "qhip_snappy_decode";
-  const int reason_base = gz ? QH_PQ_R_GZIP_BASE : zstd ? QH_PQ_R_ZSTD_BASE : QH_PQ_R_SNAPPY_BASE;
+  const bool zstd = codec == kZstd, gz = codec == kGzip, lz = codec == kLz4;
+  const std::string fn = lz ? "qhip_lz4_decode" : gz ? "qhip_gzip_decode" : zstd ? "qhip_zstd_decode" : "qhip_snappy_decode";
+  const int reason_base = lz ? QH_PQ_R_LZ4_BASE : gz ? QH_PQ_R_GZIP_BASE : zstd ? QH_PQ_R_ZSTD_BASE : QH_PQ_R_SNAPPY_BASE;
   uint64_t total_out = 0;
   for (int64_t k = 0; k < n_streams; ++k) {
     const int64_t a = src_offsets[k], b = src_offsets[k + 1];
@@ -279,7 +288,8 @@ static void unpack_decode(Ctx* ctx, UnpackCodec codec, const uint8_t* bytes, int
     qh_pq_unpack u;
     memset(&u, 0, sizeof u);
     const uint64_t len = (uint64_t)(src_offsets[k + 1] - src_offsets[k]);
-    const int bad = gz     ? qh_gzip_check_member(bytes + src_offsets[k], len, (uint64_t)dst_sizes[k], &u.start)
+    const int bad = lz     ? qh_lz4_check_sizes(len, (uint64_t)dst_sizes[k])
+                    : gz   ? qh_gzip_check_member(bytes + src_offsets[k], len, (uint64_t)dst_sizes[k], &u.start)
                     : zstd ? qh_zstd_check_frame(bytes + src_offsets[k], len, (uint64_t)dst_sizes[k], &u.start)
                            : qh_snap_check_sizes(bytes + src_offsets[k], len, (uint64_t)dst_sizes[k], &u.start);
     status[k] = bad ? reason_base + bad : QH_PQ_OK;
@@ -300,7 +310,8 @@ static void unpack_decode(Ctx* ctx, UnpackCodec codec, const uint8_t* bytes, int
   hipEvent_t ev[2] = {nullptr, nullptr};
   struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int k = 0; k < 2; ++k) if (e[k]) (void)hipEventDestroy(e[k]); } } ev_guard{ev};
   if (ctx->timing) { QHIP_HIP_CHECK(hipEventCreate(&ev[0])); QHIP_HIP_CHECK(hipEventCreate(&ev[1])); QHIP_HIP_CHECK(hipEventRecord(ev[0], ctx->stream)); }
-  if (gz) launch_pq_ungzip(buf.as<uint8_t>(), tab_d.as<qh_pq_unpack>(), nt, nullptr, st_d.as<uint32_t>(), ctx->stream);
+  if (lz) launch_pq_unlz4(buf.as<uint8_t>(), tab_d.as<qh_pq_unpack>(), nt, nullptr, st_d.as<uint32_t>(), ctx->stream);
+  else if (gz) launch_pq_ungzip(buf.as<uint8_t>(), tab_d.as<qh_pq_unpack>(), nt, nullptr, st_d.as<uint32_t>(), ctx->stream);
   else if (zstd) launch_pq_unzstd(buf.as<uint8_t>(), tab_d.as<qh_pq_unpack>(), nt, nullptr, st_d.as<uint32_t>(), ctx->stream);
   else launch_pq_unsnap(buf.as<uint8_t>(), base + area, tab_d.as<qh_pq_unpack>(), nt, nullptr, st_d.as<uint32_t>(), ctx->stream);
   if (ctx->timing) QHIP_HIP_CHECK(hipEventRecord(ev[1], ctx->stream));
@@ -329,6 +340,10 @@ void zstd_decode(Ctx* ctx, const uint8_t* bytes, int64_t n_bytes, const int64_t*
 void gzip_decode(Ctx* ctx, const uint8_t* bytes, int64_t n_bytes, const int64_t* src_offsets, const int64_t* dst_sizes, int64_t n_streams, uint8_t* out,
                  int64_t out_bytes, int32_t* status) {
   unpack_decode(ctx, kGzip, bytes, n_bytes, src_offsets, dst_sizes, n_streams, out, out_bytes, status);
+}
+void lz4_decode(Ctx* ctx, const uint8_t* bytes, int64_t n_bytes, const int64_t* src_offsets, const int64_t* dst_sizes, int64_t n_streams, uint8_t* out,
+                int64_t out_bytes, int32_t* status) {
+  unpack_decode(ctx, kLz4, bytes, n_bytes, src_offsets, dst_sizes, n_streams, out, out_bytes, status);
 }
 
 // qhip_parquet_delta_decode: k_pq_delta over raw DELTA_BINARY_PACKED streams. A refused stream is an answer (status), not an error.
@@ -443,6 +458,14 @@ int qhip_gzip_decode(qhip_ctx* ctx, const void* bytes, int64_t n_bytes, const in
   if (n_streams > 0 && (!src_offsets || !dst_sizes || !status)) return QHIP_INVALID_ARGUMENT;
   if (n_streams >= (1 << 24)) return QHIP_INVALID_ARGUMENT;
   return guarded(ctx, [&] { gzip_decode(ctx, (const uint8_t*)bytes, n_bytes, src_offsets, dst_sizes, n_streams, (uint8_t*)out, out_bytes, status); });
+}
+
+int qhip_lz4_decode(qhip_ctx* ctx, const void* bytes, int64_t n_bytes, const int64_t* src_offsets, const int64_t* dst_sizes, int64_t n_streams, void* out,
+                    int64_t out_bytes, int32_t* status) {
+  if (!ctx || n_bytes < 0 || (n_bytes > 0 && !bytes) || n_streams < 0 || out_bytes < 0 || (out_bytes > 0 && !out)) return QHIP_INVALID_ARGUMENT;
+  if (n_streams > 0 && (!src_offsets || !dst_sizes || !status)) return QHIP_INVALID_ARGUMENT;
+  if (n_streams >= (1 << 24)) return QHIP_INVALID_ARGUMENT;
+  return guarded(ctx, [&] { lz4_decode(ctx, (const uint8_t*)bytes, n_bytes, src_offsets, dst_sizes, n_streams, (uint8_t*)out, out_bytes, status); });
 }
 
 }  // extern "C"

@@ -4,11 +4,12 @@
 // its Arrow type, and the page walk that turns the projected chunks into a page table and, at format level 2, the pages of Snappy
 // chunks into an unpack table with their slots in the unpack area and, at encoding set 2, data pages V2 and the DELTA_* pages into
 // a delta table with their slots in the decoded area and, at codec set 2, the pages of ZSTD chunks into a second unpack table
-// with slots in the same unpack area and, with the gzip switch on, the pages of GZIP chunks into a third. Plain
-// C++, no Arrow, no HIP.
+// with slots in the same unpack area and, with the gzip switch on, the pages of GZIP chunks into a third and, with the lz4
+// switch on, the blocks of LZ4_RAW and legacy LZ4 pages into a fourth. Plain C++, no Arrow, no HIP.
 // A ZSTD page's frame header and block headers are checked here (qh_zstd_check_frame) before anything is reserved; its content
 // checksum, where it has one, is skipped and not verified. A GZIP page's member header and ISIZE are checked here
-// (qh_gzip_check_member); its CRC32 is skipped and not verified either.
+// (qh_gzip_check_member); its CRC32 is skipped and not verified either. An LZ4 page's size is checked against the 255x bound
+// (qh_lz4_check_sizes); a page of the legacy id is split into Hadoop's frames where they tile it (qh_lz4_hadoop_scan).
 // Every offset, length and count comes from the file and is checked before it is followed: a violation throws PqNeedsHost.
 #pragma once
 #include <cstdint>
@@ -22,6 +23,7 @@
 #include "device/qhip_delta.inc"
 #include "device/qhip_zstd.inc"
 #include "device/qhip_inflate.inc"
+#include "device/qhip_lz4.inc"
 
 static_assert(QH_PQ_R_SNAPPY_PREAMBLE == QH_PQ_R_SNAPPY_BASE + QH_SNAP_E_PREAMBLE && QH_PQ_R_SNAPPY_OFFSET == QH_PQ_R_SNAPPY_BASE + QH_SNAP_E_OFFSET &&
                   QH_PQ_R_V2_UNCOMPRESSED == QH_PQ_R_SNAPPY_BASE + QH_SNAP_E_COUNT,
@@ -32,8 +34,12 @@ static_assert(QH_PQ_R_ZSTD_BASE == QH_PQ_R_DELTA_LENGTH && QH_PQ_R_ZSTD_FRAME ==
               "the Zstd reasons follow the reasons of encoding set 2 and the decoder's error codes");
 
 static_assert(QH_PQ_R_GZIP_BASE == QH_PQ_R_ZSTD_OFFSET && QH_PQ_R_GZIP_MEMBER == QH_PQ_R_GZIP_BASE + QH_INFL_E_MEMBER &&
-                  QH_PQ_R_GZIP_TRAILER == QH_PQ_R_GZIP_BASE + QH_INFL_E_TRAILER && QH_PQ_R_COUNT == QH_PQ_R_GZIP_BASE + QH_INFL_E_COUNT,
+                  QH_PQ_R_GZIP_TRAILER == QH_PQ_R_GZIP_BASE + QH_INFL_E_TRAILER && QH_PQ_R_LZ4_SIZE == QH_PQ_R_GZIP_BASE + QH_INFL_E_COUNT,
               "the Gzip reasons follow the Zstd reasons and the decoder's error codes");
+
+static_assert(QH_PQ_R_LZ4_BASE == QH_PQ_R_GZIP_TRAILER && QH_PQ_R_LZ4_SIZE == QH_PQ_R_LZ4_BASE + QH_LZ4_E_SIZE &&
+                  QH_PQ_R_LZ4_END == QH_PQ_R_LZ4_BASE + QH_LZ4_E_END && QH_PQ_R_COUNT == QH_PQ_R_LZ4_BASE + QH_LZ4_E_COUNT,
+              "the LZ4 reasons follow the Gzip reasons and the decoder's error codes");
 
 namespace qhip_pq {
 
@@ -136,7 +142,7 @@ enum { PT_BOOLEAN = 0, PT_INT32 = 1, PT_INT64 = 2, PT_INT96 = 3, PT_FLOAT = 4, P
 enum { ENC_PLAIN = 0, ENC_PLAIN_DICTIONARY = 2, ENC_RLE = 3, ENC_BIT_PACKED = 4, ENC_DELTA_BINARY_PACKED = 5, ENC_DELTA_LENGTH_BYTE_ARRAY = 6, ENC_DELTA_BYTE_ARRAY = 7,
        ENC_RLE_DICTIONARY = 8, ENC_BYTE_STREAM_SPLIT = 9 };
 enum { PAGE_DATA = 0, PAGE_INDEX = 1, PAGE_DICTIONARY = 2, PAGE_DATA_V2 = 3 };
-enum { CODEC_UNCOMPRESSED = 0, CODEC_SNAPPY = 1, CODEC_GZIP = 2, CODEC_ZSTD = 6 };
+enum { CODEC_UNCOMPRESSED = 0, CODEC_SNAPPY = 1, CODEC_GZIP = 2, CODEC_LZ4 = 5, CODEC_ZSTD = 6, CODEC_LZ4_RAW = 7 };
 enum { L_NONE = 0, L_STRING, L_DECIMAL, L_DATE, L_TIMESTAMP, L_INT, L_OTHER };
 
 struct SchemaElem {
@@ -384,13 +390,17 @@ struct Plan {
   // the gzip switch: the pages of the GZIP chunks (k_pq_ungzip), a third table with slots in the same unpack area. `start`:
   // where the member's first DEFLATE block lies. Empty with the switch off.
   std::vector<qh_pq_unpack> ungzip;
+  // the lz4 switch: the blocks of the LZ4_RAW and legacy LZ4 chunks (k_pq_unlz4), a fourth table. A page is one bare block and
+  // one entry, or, under the legacy id where Hadoop's frames tile it, one entry per frame: each with its own source range and
+  // its own slice of the page's one slot in the same unpack area. Empty with the switch off.
+  std::vector<qh_pq_unpack> unlz4;
   // encoding set 2: the DELTA_BINARY_PACKED pages (k_pq_delta). The dense values of one get a 16-byte aligned slot of
   // num_values x width bytes in the decoded area, which lies behind the unpack area (at decoded_base) in the same buffer;
   // DELTA_LENGTH_BYTE_ARRAY lengths become entries of their column and need no slot. has_ext: some page is for k_pq_values_ext.
   std::vector<qh_pq_dstream> delta;
   uint64_t decoded_base = 0, decoded_bytes = 0;
   bool has_ext = false;
-  uint64_t packed_bytes() const { return unpack.empty() && unzstd.empty() && ungzip.empty() ? upload_bytes : unpack_base + unpack_bytes; }
+  uint64_t packed_bytes() const { return unpack.empty() && unzstd.empty() && ungzip.empty() && unlz4.empty() ? upload_bytes : unpack_base + unpack_bytes; }
   uint64_t buffer_bytes() const { return decoded_bytes ? decoded_base + decoded_bytes : packed_bytes(); }
 };
 
@@ -400,9 +410,11 @@ struct Plan {
 // DELTA_BINARY_PACKED and DELTA_LENGTH_BYTE_ARRAY. At set 1 nothing below differs from what it was before the set existed.
 // codecs: the codec set (qhip_ctx_set_parquet_codecs); 2 admits ZSTD chunks, whatever the level, which goes on governing SNAPPY.
 // At set 1 nothing below differs from what it was before the set existed either. gzip: the gzip switch
-// (qhip_ctx_set_parquet_gzip); 1 admits GZIP chunks, whatever the other three say; at 0 nothing below differs.
+// (qhip_ctx_set_parquet_gzip); 1 admits GZIP chunks, whatever the other three say; at 0 nothing below differs. lz4: the lz4
+// switch (qhip_ctx_set_parquet_lz4); 1 admits LZ4_RAW chunks (codec 7: a page is one bare LZ4 block) and chunks of the legacy id
+// (codec 5: Hadoop's frames where they tile the page, one bare block otherwise), whatever the other four say; at 0 nothing differs.
 inline Plan plan_file(const uint8_t* file, uint64_t n, const std::vector<std::string>* names, const std::vector<ArrowType>& types, const std::vector<int32_t>& proj,
-                      int level = 1, int encodings = 1, int codecs = 1, int gzip = 0) {
+                      int level = 1, int encodings = 1, int codecs = 1, int gzip = 0, int lz4 = 0) {
   const bool set2 = encodings >= 2;
   if (n >= 4 && memcmp(file, "PARE", 4) == 0) needs_host(QH_PQ_R_ENCRYPTED);
   if (n >= 4 && memcmp(file + n - 4, "PARE", 4) == 0) needs_host(QH_PQ_R_ENCRYPTED);
@@ -462,7 +474,8 @@ inline Plan plan_file(const uint8_t* file, uint64_t n, const std::vector<std::st
       const bool snappy = level >= 2 && ch.codec == CODEC_SNAPPY;
       const bool zstd = codecs >= 2 && ch.codec == CODEC_ZSTD;
       const bool gz = gzip >= 1 && ch.codec == CODEC_GZIP;
-      const bool packed = snappy || zstd || gz;
+      const bool lz = lz4 >= 1 && (ch.codec == CODEC_LZ4_RAW || ch.codec == CODEC_LZ4);
+      const bool packed = snappy || zstd || gz || lz;
       if (ch.codec != CODEC_UNCOMPRESSED && !packed) needs_host(QH_PQ_R_CODEC, G, C);
       const int64_t start = ch.dict_off > 0 ? ch.dict_off : ch.data_off;
       if (start < 4 || ch.total_compressed < 0 || (uint64_t)start > fstart || (uint64_t)ch.total_compressed > fstart - (uint64_t)start) needs_host(QH_PQ_R_CORRUPT, G, C);
@@ -517,17 +530,37 @@ inline Plan plan_file(const uint8_t* file, uint64_t n, const std::vector<std::st
           if (h.uncompressed < 0 || h.uncompressed > 0x7FFFFFFF) needs_host(QH_PQ_R_CORRUPT, G, C, pageno);
           qh_pq_unpack u;
           memset(&u, 0, sizeof u);
-          const int bad = gz   ? qh_gzip_check_member(chunk + payload + lev, (uint64_t)h.compressed - lev, (uint64_t)h.uncompressed - lev, &u.start)
-                          : zstd ? qh_zstd_check_frame(chunk + payload + lev, (uint64_t)h.compressed - lev, (uint64_t)h.uncompressed - lev, &u.start)
-                               : qh_snap_check_sizes(chunk + payload + lev, (uint64_t)h.compressed - lev, (uint64_t)h.uncompressed - lev, &u.start);
-          if (bad) needs_host((gz ? QH_PQ_R_GZIP_BASE : zstd ? QH_PQ_R_ZSTD_BASE : QH_PQ_R_SNAPPY_BASE) + bad, G, C, pageno);
-          u.src = cbuf + payload + lev; u.src_size = (uint32_t)h.compressed - lev;
-          u.dst = plan.unpack_bytes; u.dst_size = (uint32_t)h.uncompressed - lev;
+          const uint8_t* body = chunk + payload + lev;
+          const uint64_t body_bytes = (uint64_t)h.compressed - lev, declared = (uint64_t)h.uncompressed - lev;
           u.page = (uint32_t)plan.pages.size();
-          (gz ? plan.ungzip : zstd ? plan.unzstd : plan.unpack).push_back(u);
-          plan.unpack_bytes += ((uint64_t)u.dst_size + 15) & ~(uint64_t)15;
-          pg.pos = u.dst;
-          size = u.dst_size;
+          uint32_t frames = 0;
+          int frame_bad = 0;
+          if (lz && ch.codec == CODEC_LZ4 && qh_lz4_hadoop_scan(body, body_bytes, declared, &frames, &frame_bad)) {
+            // the legacy id in Hadoop's framing: an entry per frame, the frames' outputs one behind the other in the page's slot,
+            // so that the kernel knows no framing. A bare block whose first bytes happen to tile gets here too: the kernel
+            // refuses what is then no block, and the page needs the host.
+            if (frame_bad) needs_host(QH_PQ_R_LZ4_BASE + frame_bad, G, C, pageno);
+            lz4_u64 at = 0, out = 0;
+            lz4_u32 usize = 0, csize = 0;
+            while (qh_lz4_hadoop_next(body, body_bytes, &at, &usize, &csize)) {
+              u.src = cbuf + payload + lev + (at - csize); u.src_size = csize;
+              u.dst = plan.unpack_bytes + out; u.dst_size = usize;
+              plan.unlz4.push_back(u);
+              out += usize;
+            }
+          } else {
+            const int bad = lz     ? qh_lz4_check_sizes(body_bytes, declared)
+                            : gz   ? qh_gzip_check_member(body, body_bytes, declared, &u.start)
+                            : zstd ? qh_zstd_check_frame(body, body_bytes, declared, &u.start)
+                                   : qh_snap_check_sizes(body, body_bytes, declared, &u.start);
+            if (bad) needs_host((lz ? QH_PQ_R_LZ4_BASE : gz ? QH_PQ_R_GZIP_BASE : zstd ? QH_PQ_R_ZSTD_BASE : QH_PQ_R_SNAPPY_BASE) + bad, G, C, pageno);
+            u.src = cbuf + payload + lev; u.src_size = (uint32_t)body_bytes;
+            u.dst = plan.unpack_bytes; u.dst_size = (uint32_t)declared;
+            (lz ? plan.unlz4 : gz ? plan.ungzip : zstd ? plan.unzstd : plan.unpack).push_back(u);
+          }
+          pg.pos = plan.unpack_bytes;
+          size = (uint32_t)declared;
+          plan.unpack_bytes += (declared + 15) & ~(uint64_t)15;
         }
         pg.size = size;
         if (h.type == PAGE_DICTIONARY) {
@@ -586,11 +619,12 @@ inline Plan plan_file(const uint8_t* file, uint64_t n, const std::vector<std::st
     first_row += (uint64_t)g.num_rows;
   }
   // ---- the unpack area begins behind the last uploaded chunk: now its slots have their place in the buffer
-  if (!plan.unpack.empty() || !plan.unzstd.empty() || !plan.ungzip.empty()) {
+  if (!plan.unpack.empty() || !plan.unzstd.empty() || !plan.ungzip.empty() || !plan.unlz4.empty()) {
     plan.unpack_base = (plan.upload_bytes + 15) & ~(uint64_t)15;
     for (qh_pq_unpack& u : plan.unpack) u.dst += plan.unpack_base;
     for (qh_pq_unpack& u : plan.unzstd) u.dst += plan.unpack_base;
     for (qh_pq_unpack& u : plan.ungzip) u.dst += plan.unpack_base;
+    for (qh_pq_unpack& u : plan.unlz4) u.dst += plan.unpack_base;
     for (size_t p = 0; p < plan.pages.size(); ++p) {
       if (in_unpack[p] & 1) plan.pages[p].pos += plan.unpack_base;
       if (in_unpack[p] & 2) plan.pages[p].dict_pos += plan.unpack_base;

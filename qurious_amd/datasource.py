@@ -177,11 +177,13 @@ def read_parquet(path: str, columns: Optional[Sequence[str]] = None, batch_rows:
     (qhip_table_from_parquet); the result's `decoded_on_device` is True. What the device decodes is the context's
     format level (`Context.set_parquet_format` / QHIP_PARQUET_FORMAT). Level 1, the default: UNCOMPRESSED chunks — write with
     `compression="NONE"`; pyarrow's default, Snappy, takes the host path — data pages V1, PLAIN and dictionary encodings, flat
-    columns. Level 2 also decodes SNAPPY chunks, unpacked on the device; lz4 and brotli still take the host path, and so
+    columns. Level 2 also decodes SNAPPY chunks, unpacked on the device; brotli still takes the host path, and so
     does zstd unless the codec set (`Context.set_parquet_codecs` / QHIP_PARQUET_CODECS), a third independent switch, is 2: then
     ZSTD chunks are unpacked on the device as well (the frames' content checksums are not verified). So does gzip unless the
     gzip switch (`Context.set_parquet_gzip` / QHIP_PARQUET_GZIP), a fourth independent one, is on: then GZIP chunks are
-    inflated on the device (the members' CRC32 is not verified; zlib-wrapped pages still take the host path).
+    inflated on the device (the members' CRC32 is not verified; zlib-wrapped pages still take the host path). And so does lz4
+    unless the lz4 switch (`Context.set_parquet_lz4` / QHIP_PARQUET_LZ4), a fifth independent one, is on: then LZ4_RAW chunks
+    (`compression="lz4"`) and chunks of the legacy LZ4 id, Hadoop-framed or bare, are unpacked on the device.
     Which page kinds and encodings are decoded is a second, independent switch, the encoding set
     (`Context.set_parquet_encodings` / QHIP_PARQUET_ENCODINGS). Set 1, the default: data pages V1 with PLAIN or dictionary
     values. Set 2 also decodes data pages V2 (`data_page_version="2.0"`), RLE Boolean values, BYTE_STREAM_SPLIT,

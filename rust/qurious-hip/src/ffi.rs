@@ -264,6 +264,18 @@ extern "C" {
         out_bytes: i64,
         status: *mut i32,
     ) -> c_int;
+    pub fn qhip_ctx_set_parquet_lz4(ctx: *mut qhip_ctx, on: i32) -> c_int;
+    pub fn qhip_lz4_decode(
+        ctx: *mut qhip_ctx,
+        bytes: *const c_void,
+        n_bytes: i64,
+        src_offsets: *const i64,
+        dst_sizes: *const i64,
+        n_streams: i64,
+        out: *mut c_void,
+        out_bytes: i64,
+        status: *mut i32,
+    ) -> c_int;
     pub fn qhip_ctx_parquet_delta_ms(ctx: *const qhip_ctx, out: *mut f64) -> c_int;
     pub fn qhip_table_to_arrow(
         ctx: *mut qhip_ctx,

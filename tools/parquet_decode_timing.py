@@ -20,7 +20,8 @@ compressed and uncompressed; (c) copies the compressed bytes, which are what cro
 ZSTD (the writer's default level) and sets codec set 2 (Context.set_parquet_codecs); the unpack pass is then k_pq_unzstd.
 --compression gzip writes them with GZIP at level 6 — zlib's own default and what most writers use; pyarrow's default, 9, takes
 minutes per GB to write — and sets the gzip switch (Context.set_parquet_gzip); the unpack pass is then k_pq_ungzip. While a
-compressed file is written a progress line goes to stderr every 8 row groups.
+compressed file is written a progress line goes to stderr every 8 row groups. --compression lz4 writes them with LZ4_RAW, one
+bare LZ4 block per page, and sets the lz4 switch (Context.set_parquet_lz4); the unpack pass is then k_pq_unlz4.
 
 --page-version 2.0 writes data pages V2 and --encoding plain|delta|bss writes without dictionaries, with PLAIN values, with
 DELTA_BINARY_PACKED integers and dates and DELTA_LENGTH_BYTE_ARRAY strings, or with BYTE_STREAM_SPLIT numbers; either sets
@@ -28,7 +29,7 @@ encoding set 2 (Context.set_parquet_encodings). (d) then also has the delta pass
 k_pq_strings); the time of k_pq_values includes k_pq_values_ext, which runs right behind it.
 
     python tools/parquet_decode_timing.py [--gb 1.0] [--runs 10] [--warmup 2] [--repeat 2] [--threads 16] [--columns l_quantity,l_shipdate]
-                                          [--compression none|snappy|zstd|gzip] [--page-version 1.0|2.0] [--encoding plain|delta|bss]
+                                          [--compression none|snappy|zstd|gzip|lz4] [--page-version 1.0|2.0] [--encoding plain|delta|bss]
 """
 import argparse
 import ctypes as C
@@ -67,8 +68,8 @@ def writer_options(schema, page_version, encoding):
 
 def write_file(path, target_bytes, compression="none", page_version="1.0", encoding=None):
     """lineitem rows, one row group per 2^20 of them, until the file has about target_bytes; returns the row count.
-    compression="snappy" / "zstd" / "gzip": the rows the uncompressed file would have, written with pyarrow's defaults / with ZSTD /
-    with GZIP at level 6"""
+    compression="snappy" / "zstd" / "gzip" / "lz4": the rows the uncompressed file would have, written with pyarrow's defaults /
+    with ZSTD / with GZIP at level 6 / with LZ4_RAW"""
     step, rows = 1 << 20, 0
     schema = pa.schema([pa.field(f.name, f.type) for f in synth.LINEITEM_SCHEMA])
     group = lambda first: pa.Table.from_batches([synth.lineitem_batch(first, step)]).cast(schema)   # noqa: E731
@@ -112,8 +113,8 @@ def main():
     ap.add_argument("--repeat", type=int, default=2)
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--columns", type=str, default="", help="comma-separated projection (default: every column)")
-    ap.add_argument("--compression", choices=["none", "snappy", "zstd", "gzip"], default="none",
-                    help="snappy: pyarrow's defaults, decoded at format level 2; zstd: decoded at codec set 2; gzip: decoded with the gzip switch on")
+    ap.add_argument("--compression", choices=["none", "snappy", "zstd", "gzip", "lz4"], default="none",
+                    help="snappy: pyarrow's defaults, decoded at format level 2; zstd: decoded at codec set 2; gzip / lz4: decoded with the gzip / lz4 switch on")
     ap.add_argument("--page-version", choices=["1.0", "2.0"], default="1.0", help="2.0: data pages V2, decoded at encoding set 2")
     ap.add_argument("--encoding", choices=["plain", "delta", "bss"], default=None, help="no dictionaries; delta and bss are decoded at encoding set 2")
     args = ap.parse_args()
@@ -126,6 +127,8 @@ def main():
         ctx.set_parquet_codecs(2)
     if args.compression == "gzip":
         ctx.set_parquet_gzip(1)
+    if args.compression == "lz4":
+        ctx.set_parquet_lz4(1)
     if args.page_version == "2.0" or args.encoding in ("delta", "bss"):
         ctx.set_parquet_encodings(2)
     hip = C.CDLL(None)   # (libqhip.so is loaded globally and brings the HIP runtime with it)
@@ -184,7 +187,7 @@ def main():
             if k == 0 and args.compression != "none":
                 med = statistics.median(p[5] for p in per)
                 kernels += med
-                print(f"(d) { {'snappy': 'k_pq_unsnap', 'zstd': 'k_pq_unzstd', 'gzip': 'k_pq_ungzip'}[args.compression] + ' (unpack)':32s} {med:9.3f} ms  {plain_bytes / max(med, 1e-6) / 1e6:9.1f} GB/s of uncompressed bytes", flush=True)
+                print(f"(d) { {'snappy': 'k_pq_unsnap', 'zstd': 'k_pq_unzstd', 'gzip': 'k_pq_ungzip', 'lz4': 'k_pq_unlz4'}[args.compression] + ' (unpack)':32s} {med:9.3f} ms  {plain_bytes / max(med, 1e-6) / 1e6:9.1f} GB/s of uncompressed bytes", flush=True)
             if k == 1 and args.encoding == "delta":
                 med = statistics.median(p[6] for p in per)
                 kernels += med
