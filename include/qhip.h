@@ -383,7 +383,8 @@ int qhip_ctx_json_pass_ms(const qhip_ctx* ctx, double* out, int32_t n_out);
  * switch, qhip_ctx_set_parquet_gzip below, takes GZIP, and the lz4 switch, qhip_ctx_set_parquet_lz4 below, LZ4_RAW and the legacy
  * LZ4 id; brotli and zlib-wrapped pages stay on the host), data pages V2 (encoding set 1; qhip_ctx_set_parquet_encodings below), index
  * pages, an encrypted footer, a group / list / map field anywhere in the schema, a chunk with file_path, any other encoding
- * (DELTA_*, BYTE_STREAM_SPLIT, RLE values; encoding set 2 decodes these but DELTA_BYTE_ARRAY), BIT_PACKED levels, every other type pair (a zoned Timestamp, Date64, Time, Float16,
+ * (DELTA_*, BYTE_STREAM_SPLIT, RLE values; encoding set 2 decodes these but DELTA_BYTE_ARRAY, which has a switch of its own,
+ * qhip_ctx_set_parquet_delta_byte_array below), BIT_PACKED levels, every other type pair (a zoned Timestamp, Date64, Time, Float16,
  * Decimal256, INT96, LargeUtf8, Binary, dictionary-typed fields), a stored value outside an Int8/Int16/UInt8/UInt16 column's
  * range, a Utf8 column over 2^31 - 1 bytes, more than 64 projected columns, 0 rows, 2^32 - 1 rows or more, and every offset,
  * length, count or index that points outside the file, its chunk, its page or its dictionary ("corrupt"): no host or device
@@ -413,7 +414,7 @@ int qhip_ctx_set_parquet_format(qhip_ctx* ctx, int32_t level);
  * 65536, miniblocks dividing it into multiples of 32 values, wrapping arithmetic in the type's width); DELTA_LENGTH_BYTE_ARRAY
  * for Utf8. Delta pages are decoded by a pass of their own (k_pq_delta) and the new value encodings by a second instance of the
  * values kernel; a file with none of them launches what set 1 launches.
- * Still needs the host at set 2: DELTA_BYTE_ARRAY (every value needs its predecessor's bytes), RLE values of anything but
+ * Still needs the host at set 2: DELTA_BYTE_ARRAY unless its own switch is on (qhip_ctx_set_parquet_delta_byte_array below), RLE values of anything but
  * BOOLEAN, delta blocks above 65536 values, and everything else on the list
  * above (nested columns, other codecs, INT96, ...).
  * Any other set answers QHIP_INVALID_ARGUMENT and leaves the set as it was. The environment's QHIP_PARQUET_ENCODINGS (1 / 2) is
@@ -465,6 +466,39 @@ int qhip_ctx_set_parquet_gzip(qhip_ctx* ctx, int32_t on);
  * file without LZ4 chunks launches what it launches with the switch off. Any other value answers QHIP_INVALID_ARGUMENT and
  * leaves the switch as it was. The environment's QHIP_PARQUET_LZ4 (0 / 1) is read when the context is created. */
 int qhip_ctx_set_parquet_lz4(qhip_ctx* ctx, int32_t on);
+/* Whether qhip_table_from_parquet decodes DELTA_BYTE_ARRAY data pages on the device: a sixth switch, independent of the format
+ * level, the encoding set, the codec set, the gzip switch and the lz4 switch, none of which it changes. on 0 (the default): such
+ * a page is "a value encoding other than PLAIN and RLE_DICTIONARY" and needs the host. on 1: the encoding is taken for Utf8
+ * columns (BYTE_ARRAY) and for the FIXED_LEN_BYTE_ARRAY(1..16) decimals, what arrow-rs writes at writer version 2 once a
+ * dictionary outgrows its page or where dictionaries are off. A data page V1 needs nothing else; a data page V2 still needs
+ * encoding set 2 and a compressed chunk its codec's switch. The page's values are a DELTA_BINARY_PACKED stream of prefix
+ * lengths, a second one of suffix lengths and the suffix bytes: one wavefront per page decodes both streams (k_pq_delta_dba, a second instance of k_pq_delta's body), and a
+ * kernel of its own (k_pq_dba_fill) reconstructs the prefixes 64 rows per step instead of value by value — for a decimal page
+ * before the call's one host wait, dense into the decoded area; for a Utf8 column behind it, straight into the column's data.
+ * Needs the host ("DELTA_BYTE_ARRAY"): a page whose first prefix length is not 0 (Arrow's writer and reader reset the previous
+ * value at every page; the writers of PARQUET-246 did not), a negative prefix or suffix length, a prefix longer than the value
+ * before it, suffix lengths that add up past the page, a value above 2^31 - 1 bytes, a decimal value whose length is not the
+ * column's width, and whatever DELTA_BINARY_PACKED forbids in either stream. A file without such pages launches what it
+ * launches with the switch off. Any other value answers QHIP_INVALID_ARGUMENT and leaves the switch as it was. The
+ * environment's QHIP_PARQUET_DBA (0 / 1) is read when the context is created. */
+int qhip_ctx_set_parquet_delta_byte_array(qhip_ctx* ctx, int32_t on);
+/* Device time (ms) of the fill passes (the DELTA_BYTE_ARRAY switch: k_pq_dba_fill over the decimal pages, behind the delta pass,
+ * plus k_pq_dba_fill over the Utf8 columns, behind "Utf8") of the last qhip_table_from_parquet, or of the last
+ * qhip_parquet_dba_decode's fill kernel, when the context's timing is on; 0 otherwise and for a file without such pages. It
+ * belongs to none of qhip_ctx_parquet_pass_ms's five values; the two length streams are part of the delta pass. */
+int qhip_ctx_parquet_fill_ms(const qhip_ctx* ctx, double* out);
+/* A testing and measurement aid: the device DELTA_BYTE_ARRAY decoder of the switch above over raw value streams (a page's bytes
+ * behind its levels). bytes, src_offsets: as for qhip_parquet_delta_decode below; widths[k]: the FIXED_LEN_BYTE_ARRAY width every
+ * value of stream k must have (1..16), or 0 for BYTE_ARRAY; counts[k]: the number of values the caller expects (at most 2^28 - 1
+ * in all). The kernels are the ones a file goes through. The values of the decoded streams lie one behind the other in out;
+ * value_offsets has counts[k] + 1 entries per stream, one stream behind the other: where each value of stream k begins in out,
+ * and where its last one ends (a refused stream: counts[k] + 1 times the same position). total_bytes: the bytes of all values;
+ * where out_bytes is smaller, nothing is written to out and the caller calls again with room. status[k]: 0, or the Parquet
+ * needs-host reason (QH_PQ_R_DBA_*, QH_PQ_R_DELTA_*) for which stream k was refused — a normal return, and the other streams of
+ * the call are decoded all the same. */
+int qhip_parquet_dba_decode(qhip_ctx* ctx, const void* bytes, int64_t n_bytes, const int64_t* src_offsets, const int32_t* widths,
+                            const int64_t* counts, int64_t n_streams, void* out, int64_t out_bytes, int64_t* value_offsets,
+                            int64_t* total_bytes, int32_t* status);
 /* Device time (ms) of the delta pass (encoding set 2: DELTA_* pages -> the decoded area) of the last qhip_table_from_parquet, or
  * of the last qhip_parquet_delta_decode's kernel, when the context's timing is on; 0 otherwise and for a file without such
  * pages. The pass runs between "levels" and "string walk" and belongs to neither of qhip_ctx_parquet_pass_ms's five values. */

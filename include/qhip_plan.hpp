@@ -55,6 +55,9 @@ class Context {
   void set_parquet_gzip(int on) const { check(qhip_ctx_set_parquet_gzip(ctx_, on)); }
   // ... and its lz4 switch (qhip.h: 0 off, 1 LZ4_RAW and legacy LZ4 chunks are unpacked on the device), independent of the four above
   void set_parquet_lz4(int on) const { check(qhip_ctx_set_parquet_lz4(ctx_, on)); }
+  // ... and its DELTA_BYTE_ARRAY switch (qhip.h: 0 off, 1 such pages of Utf8 and FIXED_LEN_BYTE_ARRAY decimal columns are decoded on
+  // the device), independent of the five above
+  void set_parquet_delta_byte_array(int on) const { check(qhip_ctx_set_parquet_delta_byte_array(ctx_, on)); }
 
  private:
   qhip_ctx* ctx_ = nullptr;

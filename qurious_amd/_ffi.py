@@ -164,6 +164,9 @@ def load_library() -> C.CDLL:
             "qhip_gzip_decode": (C.c_int, [vp, vp, i64, P(i64), P(i64), i64, vp, i64, P(i32)]),
             "qhip_ctx_set_parquet_lz4": (C.c_int, [vp, i32]),
             "qhip_lz4_decode": (C.c_int, [vp, vp, i64, P(i64), P(i64), i64, vp, i64, P(i32)]),
+            "qhip_ctx_set_parquet_delta_byte_array": (C.c_int, [vp, i32]),
+            "qhip_ctx_parquet_fill_ms": (C.c_int, [vp, P(C.c_double)]),
+            "qhip_parquet_dba_decode": (C.c_int, [vp, vp, i64, P(i64), P(i32), P(i64), i64, vp, i64, P(i64), P(i64), P(i32)]),
             "qhip_ctx_parquet_delta_ms": (C.c_int, [vp, P(C.c_double)]),
             "qhip_parquet_delta_decode": (C.c_int, [vp, vp, i64, P(i64), P(i32), P(i64), i64, vp, i64, P(i64), P(i32)]),
             "qhip_table_to_arrow": (C.c_int, [vp, vp, i64, vp, vp]),
@@ -341,6 +344,55 @@ class Context:
         of the legacy LZ4 id (Hadoop's length frames where they tile the page, one bare block otherwise) are unpacked on the
         device, one wavefront per block. QHIP_PARQUET_LZ4 sets it when the context is made."""
         self.check(self.lib.qhip_ctx_set_parquet_lz4(self.handle, int(on)))
+
+    def set_parquet_delta_byte_array(self, on: int):
+        """The device Parquet decoder's DELTA_BYTE_ARRAY switch, independent of the format level, the encoding set, the codec set,
+        the gzip switch and the lz4 switch: 0 (the default) a DELTA_BYTE_ARRAY page takes the host path; 1 such pages of Utf8
+        columns and of FIXED_LEN_BYTE_ARRAY decimals are decoded on the device, the two length streams by k_pq_delta_dba and the
+        prefixes by k_pq_dba_fill, 64 rows per step. A page whose first prefix is not 0 stays on the host. QHIP_PARQUET_DBA
+        sets it when the context is made."""
+        self.check(self.lib.qhip_ctx_set_parquet_delta_byte_array(self.handle, int(on)))
+
+    def parquet_fill_ms(self) -> float:
+        """Device time (ms) of the fill passes (k_pq_dba_fill, the DELTA_BYTE_ARRAY switch) of the last device Parquet decode, or
+        of the last `dba_decode`'s fill kernel (timing on). It is part of none of `parquet_pass_ms`'s five values."""
+        out = C.c_double(0)
+        self.check(self.lib.qhip_ctx_parquet_fill_ms(self.handle, C.byref(out)))
+        return float(out.value)
+
+    def dba_decode(self, streams: Sequence[bytes], widths: Sequence[int], counts: Sequence[int]):
+        """A testing and measurement aid (qhip_parquet_dba_decode): raw DELTA_BYTE_ARRAY value streams through the kernels of the
+        DELTA_BYTE_ARRAY switch, in one call. `widths[k]`: the FIXED_LEN_BYTE_ARRAY width of stream k's values, 0 for
+        BYTE_ARRAY; `counts[k]`: the values expected. Returns (values, statuses): statuses[k] is 0 or the needs-host reason for
+        which stream k was refused, values[k] its values as a list of bytes (None when refused)."""
+        n = len(streams)
+        blob = b"".join(streams)
+        offs = (C.c_int64 * (n + 1))()
+        at = 0
+        for k, s in enumerate(streams):
+            offs[k] = at
+            at += len(s)
+        offs[n] = at
+        w = (C.c_int32 * max(n, 1))(*[int(v) for v in widths])
+        c = (C.c_int64 * max(n, 1))(*[int(v) for v in counts])
+        nvo = sum(int(v) + 1 for v in counts)
+        vo = (C.c_int64 * max(nvo, 1))()
+        status = (C.c_int32 * max(n, 1))()
+        total = C.c_int64(0)
+        room = max(1 << 16, 8 * len(blob))
+        while True:
+            out = C.create_string_buffer(room)
+            self.check(self.lib.qhip_parquet_dba_decode(self.handle, blob, len(blob), offs, w, c, n, out, room, vo, C.byref(total), status))
+            if total.value <= room:
+                break
+            room = int(total.value)
+        raw = out.raw
+        values, at = [], 0
+        for k in range(n):
+            cnt = int(counts[k])
+            values.append(None if status[k] else [raw[vo[at + i]:vo[at + i + 1]] for i in range(cnt)])
+            at += cnt + 1
+        return values, [int(status[k]) for k in range(n)]
 
     def parquet_delta_ms(self) -> float:
         """Device time (ms) of the delta pass (k_pq_delta, encoding set 2) of the last device Parquet decode, or of the last

@@ -334,6 +334,12 @@ struct Ctx {
   // ... and its lz4 switch, independent of all four: 1 = + LZ4_RAW and legacy LZ4 chunks (k_pq_unlz4); QHIP_PARQUET_LZ4 at
   // context creation, qhip_ctx_set_parquet_lz4 later
   int parquet_lz4 = 0;
+  // ... and its DELTA_BYTE_ARRAY switch, independent of all five: 1 = + data pages of that encoding in Utf8 columns and
+  // FIXED_LEN_BYTE_ARRAY decimals (k_pq_delta, k_pq_dba_fill); QHIP_PARQUET_DBA at context creation,
+  // qhip_ctx_set_parquet_delta_byte_array later
+  int parquet_dba = 0;
+  // device time of the fill passes (k_pq_dba_fill, behind the delta pass and behind "Utf8"): 0 for a file without DELTA_BYTE_ARRAY pages
+  float parquet_fill_ms = 0;
   // device time of the delta pass (k_pq_delta, between "levels" and "string walk"): 0 for a file without DELTA_* pages
   float parquet_delta_ms = 0;
   // the device CSV decoder's grammar level (csv.cpp): 1 = plain fields only, 2 = + canonical quoted fields, Boolean, Timestamp;

@@ -355,6 +355,7 @@ int qhip_ctx_create(int device_index, qhip_ctx** out) {
     c->parquet_codecs = env_int("QHIP_PARQUET_CODECS", 1) == 2 ? 2 : 1;
     c->parquet_gzip = env_int("QHIP_PARQUET_GZIP", 0) == 1 ? 1 : 0;
     c->parquet_lz4 = env_int("QHIP_PARQUET_LZ4", 0) == 1 ? 1 : 0;
+    c->parquet_dba = env_int("QHIP_PARQUET_DBA", 0) == 1 ? 1 : 0;
     c->pinned_bytes = 256 * 1024;
     QHIP_HIP_CHECK(hipHostMalloc(&c->pinned, c->pinned_bytes, hipHostMallocDefault));
     memset(&c->stats, 0, sizeof(c->stats));
@@ -452,6 +453,12 @@ int qhip_ctx_set_parquet_gzip(qhip_ctx* ctx, int32_t on) {
 int qhip_ctx_set_parquet_lz4(qhip_ctx* ctx, int32_t on) {
   if (!ctx || on < 0 || on > 1) return QHIP_INVALID_ARGUMENT;
   ctx->parquet_lz4 = on;
+  return QHIP_OK;
+}
+
+int qhip_ctx_set_parquet_delta_byte_array(qhip_ctx* ctx, int32_t on) {
+  if (!ctx || on < 0 || on > 1) return QHIP_INVALID_ARGUMENT;
+  ctx->parquet_dba = on;
   return QHIP_OK;
 }
 

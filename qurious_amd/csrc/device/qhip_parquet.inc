@@ -107,7 +107,11 @@ typedef long long pq_i64;
 #define QH_PQ_R_LZ4_OUTPUT 72      // a literal run or a match past uncompressed_page_size
 #define QH_PQ_R_LZ4_OFFSET 73      // a match offset of 0 or beyond the bytes produced
 #define QH_PQ_R_LZ4_END 74         // input left behind a full output; input that ends with output missing, or behind a match
-#define QH_PQ_R_COUNT 75
+// (the DELTA_BYTE_ARRAY switch, qhip_ctx_set_parquet_delta_byte_array: device/qhip_dba.inc)
+#define QH_PQ_R_DBA_PREFIX 75      // a negative prefix length, a first prefix of the page that is not 0, a prefix longer than the value before it
+#define QH_PQ_R_DBA_SUFFIX 76      // a negative suffix length, suffix lengths that add up past the page, a value longer than 2^31 - 1
+#define QH_PQ_R_DBA_WIDTH 77       // a FIXED_LEN_BYTE_ARRAY value whose length is not the column's width
+#define QH_PQ_R_COUNT 78
 
 QH_PQ_HD inline const char* qh_pq_reason_text(unsigned r) {
   switch (r) {
@@ -185,6 +189,9 @@ QH_PQ_HD inline const char* qh_pq_reason_text(unsigned r) {
     case QH_PQ_R_LZ4_OUTPUT: return "corrupt: an LZ4 literal run or match past uncompressed_page_size";
     case QH_PQ_R_LZ4_OFFSET: return "corrupt: an LZ4 match offset of 0 or beyond the bytes produced";
     case QH_PQ_R_LZ4_END: return "corrupt: an LZ4 page whose input and output do not end together behind a literal run";
+    case QH_PQ_R_DBA_PREFIX: return "a DELTA_BYTE_ARRAY prefix length that is negative, not 0 at the head of its page, or longer than the value before it";
+    case QH_PQ_R_DBA_SUFFIX: return "corrupt: a DELTA_BYTE_ARRAY suffix length that is negative or points past its page, or a value above 2 GiB";
+    case QH_PQ_R_DBA_WIDTH: return "corrupt: a DELTA_BYTE_ARRAY value of a fixed-length column whose length is not the column's width";
     default: return "outside the device's Parquet coverage";
   }
 }
@@ -198,6 +205,8 @@ QH_PQ_HD inline const char* qh_pq_reason_text(unsigned r) {
 #define QH_PQ_ENC_BSS 4u        // BYTE_STREAM_SPLIT: byte j of value idx at j * (non-NULL rows) + idx
 #define QH_PQ_ENC_DELTA 5u      // DELTA_BINARY_PACKED: k_pq_delta leaves the values dense (PLAIN) in the page's slot at dict_pos
 #define QH_PQ_ENC_DELTA_LEN 6u  // DELTA_LENGTH_BYTE_ARRAY: k_pq_delta writes the page's (length, position) entries
+// (the DELTA_BYTE_ARRAY switch. A FIXED_LEN_BYTE_ARRAY page of that encoding is QH_PQ_ENC_DELTA: k_pq_dba_fill leaves its values dense)
+#define QH_PQ_ENC_DBA 7u        // DELTA_BYTE_ARRAY, Utf8: k_pq_delta writes the page's (length, suffix position, prefix length) entries
 
 #define QH_PQ_F_V2 1u           // a data page V2: its levels lie at lev_pos without a length prefix, its values begin at pos
 
@@ -236,9 +245,25 @@ typedef struct qh_pq_dstream {
   pq_u32 src_size;
   pq_u32 count;       // raw: the expected number of values
   pq_u32 page;        // index into the page table (the offender word), or the stream's number
-  pq_u32 width;       // 4 or 8: the physical type's bytes; | QH_PQ_DS_LENGTHS for DELTA_LENGTH_BYTE_ARRAY
+  pq_u32 width;       // 4 or 8: the physical type's bytes; | QH_PQ_DS_LENGTHS for DELTA_LENGTH_BYTE_ARRAY; QH_PQ_DS_DBA, below
 } qh_pq_dstream;
 #define QH_PQ_DS_LENGTHS 0x100u
+// DELTA_BYTE_ARRAY: the stream of prefix lengths, behind it the stream of suffix lengths, behind that the suffix bytes. The low
+// byte of width is the FIXED_LEN_BYTE_ARRAY width every value must have, 0 for BYTE_ARRAY. The entries go to the column's entry
+// array (a Utf8 page) or, 16 bytes each, to `dst` (a FIXED_LEN_BYTE_ARRAY page, a raw stream).
+#define QH_PQ_DS_DBA 0x200u
+
+// one DELTA_BYTE_ARRAY page for k_pq_dba_fill. Row space (a Utf8 column, after the host wait): the rows [first, first + n) of
+// the column. Value space (a FIXED_LEN_BYTE_ARRAY page, before the wait): the page's entries lie at buffer[first ..), its dense
+// values go to buffer[out ..), `width` bytes each; their count is the level pass's non-NULL count of page `page`.
+typedef struct qh_pq_fill {
+  pq_u64 first;
+  pq_u64 out;
+  pq_u32 n;
+  pq_u32 page;
+  pq_u32 width;
+  pq_u32 col;         // row space: the column (host side only)
+} qh_pq_fill;
 
 // one compressed page (format level 2): k_pq_unsnap turns buffer[src .. src + src_size) into buffer[dst .. dst + dst_size).
 // Codec set 2 keeps the ZSTD pages in a second table of the same entries for k_pq_unzstd: `start` is then where the frame's
@@ -255,7 +280,9 @@ typedef struct qh_pq_unpack {
   pq_u32 start;       // bytes of the preamble: where the elements begin in the payload
 } qh_pq_unpack;
 
-typedef struct qh_pq_ent { pq_u64 pos; pq_u32 len; pq_u32 pad; } qh_pq_ent;   // one BYTE_ARRAY value: its bytes in the buffer
+// one BYTE_ARRAY value: its bytes in the buffer. Of a DELTA_BYTE_ARRAY page: len is prefix + suffix, pos where the suffix bytes
+// lie, pad the prefix length; everywhere else pad is 0.
+typedef struct qh_pq_ent { pq_u64 pos; pq_u32 len; pq_u32 pad; } qh_pq_ent;
 
 typedef struct qh_pq_col {
   void* values;       // width-byte values | u32 lengths (Utf8, scanned into offsets afterwards) | Boolean bits (zeroed)
@@ -266,6 +293,7 @@ typedef struct qh_pq_col {
   pq_u32 flba;        // FIXED_LEN_BYTE_ARRAY length 1..16
   pq_u32 width;       // bytes of an output value: 1, 2, 4, 8, 16 (0: Boolean, Utf8)
   pq_u32 narrow;      // 0: none; 1: signed, 2: unsigned range check of an INT32 stored for a 1- / 2-byte column
+  pq_u32* prefix;     // Utf8 with a DELTA_BYTE_ARRAY page: row k's prefix length, zeroed; NULL for every other column
 } qh_pq_col;
 
 // what the level pass leaves for the value passes, per page

@@ -13,6 +13,8 @@
 //   k_pq_delta    encoding set 2 only: a DELTA_BINARY_PACKED stream -> dense values in the decoded area, or a Utf8 page's entries
 //   k_pq_values   64 rows per step: rank among the non-NULL rows -> value index -> run cursor -> dictionary gather or PLAIN read
 //   k_pq_values_ext  encoding set 2 only: the same body for RLE Boolean, BYTE_STREAM_SPLIT and DELTA_* pages
+//   k_pq_delta_dba  the DELTA_BYTE_ARRAY switch only: k_pq_delta's body for a page's prefix and suffix lengths -> its entries
+//   k_pq_dba_copy / k_pq_dba_fill  the DELTA_BYTE_ARRAY switch only: suffixes into place, then the prefixes, 64 rows per step
 //
 // Nothing here trusts the file: every run, index and length is checked against its stream, dictionary or page before it is
 // followed, and the first offender (page << 8 | reason) makes the whole call answer "needs host".
@@ -110,7 +112,7 @@ __global__ __launch_bounds__(64) void k_pq_strings(const u8* __restrict__ buf, u
   if (page >= npages) return;
   const qh_pq_page pg = pages[page];
   const qh_pq_col col = cols[pg.col];
-  if (col.phys != QH_PQ_P_BYTES || pg.enc == QH_PQ_ENC_DICT || pg.enc == QH_PQ_ENC_DELTA_LEN) return;   // (k_pq_delta wrote a DELTA_LENGTH page's entries)
+  if (col.phys != QH_PQ_P_BYTES || pg.enc == QH_PQ_ENC_DICT || pg.enc == QH_PQ_ENC_DELTA_LEN || pg.enc == QH_PQ_ENC_DBA) return;   // (k_pq_delta wrote a DELTA_LENGTH or DELTA_BYTE_ARRAY page's entries)
   if (__hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != ~0ULL) return;   // (the level pass found an offender: its state is void)
   const int lane = qh_lane();
   u64 base = pg.pos, size = pg.size, count = pg.num_values;
@@ -292,7 +294,10 @@ __global__ __launch_bounds__(64) void k_pq_unlz4(u8* buf, const qh_pq_unpack* __
 // Encoding set 2 adds a second instance of the same body, k_pq_values_ext, for the pages k_pq_values leaves alone: RLE Boolean
 // values (the run cursor at width 1, the "index" taken as the bit, no dictionary), BYTE_STREAM_SPLIT (one more gather),
 // DELTA_BINARY_PACKED (read as PLAIN from the slot k_pq_delta filled) and DELTA_LENGTH_BYTE_ARRAY (the entries k_pq_delta
-// wrote). It is launched only for a file that has such a page; kExt = false compiles to the kernel of encoding set 1.
+// wrote) and, with the DELTA_BYTE_ARRAY switch, DELTA_BYTE_ARRAY: a Utf8 page's entries, whose prefix lengths are scattered to
+// the column's per-row array beside length and position; a FIXED_LEN_BYTE_ARRAY page arrives as QH_PQ_ENC_DELTA, dense in its
+// slot behind k_pq_dba_fill. It is launched only for a file that has such a page; kExt = false compiles to the kernel of
+// encoding set 1.
 template <bool kExt>
 __device__ __forceinline__ void pq_values_body(const u8* __restrict__ buf, const qh_pq_page* __restrict__ pages, u32 npages, const qh_pq_col* __restrict__ cols,
                                                const qh_pq_state* __restrict__ state, u64* err, u64* utf8_bytes) {
@@ -371,6 +376,8 @@ __device__ __forceinline__ void pq_values_body(const u8* __restrict__ buf, const
       if (col.phys == QH_PQ_P_BYTES) {
         const qh_pq_ent e = col.ent[pg.ent + (dict ? (u64)index : idx)];
         spos = e.pos; slen_row = e.len;
+        // (a DELTA_BYTE_ARRAY page: pos is where the suffix lies, and the row's prefix length goes to the column's zeroed array)
+        if (kExt && pg.enc == QH_PQ_ENC_DBA && col.prefix) col.prefix[row] = e.pad;
       } else if (col.phys == QH_PQ_P_BOOL) {
         bit = rleb ? index != 0 : (v[idx >> 3] >> (idx & 7)) & 1;
       } else if (bss) {
@@ -432,111 +439,280 @@ __device__ __forceinline__ u64 pq_lane63(u64 v) {
 // itself (entry i > 0 belongs to lane (i - 1) & 63: a block is a multiple of 128 values) once the walk is over.
 // Every loop advances by a block that holds a value and at least one byte, or by 64 values of it: bounded by the count, which
 // the page's rows bound, and by the stream's bytes. A refused stream leaves its slot half written; nobody reads it.
-__global__ __launch_bounds__(64) void k_pq_delta(u8* buf, const qh_pq_dstream* __restrict__ tab, u32 n, const qh_pq_page* __restrict__ pages,
-                                                 const qh_pq_col* __restrict__ cols, const qh_pq_state* __restrict__ state, u64* err, u32* status, u64* ends) {
+// The DELTA_BYTE_ARRAY switch: a stream marked QH_PQ_DS_DBA is walked twice by the same code, first the prefix lengths, which
+// go to the pad field of the entries, then, from where that stream ended, the suffix lengths, which become the entries' length
+// (prefix + suffix) and the position of the suffix bytes as a DELTA_LENGTH_BYTE_ARRAY page's lengths do. The second walk reads
+// back the prefix lengths the first one stored, from whichever lane: k_pq_unsnap's rule, with its fence between the walks. Each
+// length is checked (device/qhip_dba.inc) before anything is made of it; of several offenders in a step the lowest lane's counts.
+// Those streams have an instance of the body of their own, k_pq_delta_dba, launched only where there is one, so that
+// k_pq_delta compiles to what it was; each instance leaves the other's streams alone.
+template <bool kDba>
+__device__ __forceinline__ void pq_delta_body(u8* buf, const qh_pq_dstream* __restrict__ tab, u32 n, const qh_pq_page* __restrict__ pages,
+                                              const qh_pq_col* __restrict__ cols, const qh_pq_state* __restrict__ state, u64* err, u32* status, u64* ends) {
   const u32 k = blockIdx.x;
   if (k >= n) return;
   const qh_pq_dstream t = tab[k];
+  if (kDba != ((t.width & QH_PQ_DS_DBA) != 0)) return;
   const int lane = qh_lane();
   u64 src = t.src, size = t.src_size, count = t.count;
+  const bool dba = kDba;
   const bool lengths = t.width & QH_PQ_DS_LENGTHS;
-  const u32 width = t.width & 0xFFu, bits = width * 8;
-  qh_pq_ent* ent = nullptr;
+  const u32 width = t.width & 0xFFu, bits = dba ? 32u : width * 8;
+  qh_pq_ent* ent = dba ? (qh_pq_ent*)(buf + t.dst) : nullptr;
   if (pages) {
     if (__hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != ~0ULL) return;   // (the level pass found an offender: its state is void)
     const qh_pq_page pg = pages[t.page];
     const qh_pq_state st = state[t.page];
     src = pg.pos + st.values_off; size = (u64)pg.size - st.values_off; count = st.nonnull;
     if (!count) return;   // (a page without non-NULL rows is not looked at beyond its levels)
-    if (lengths) ent = cols[pg.col].ent + pg.ent;
+    if (lengths || (dba && !width)) ent = cols[pg.col].ent + pg.ent;
   }
-  const u8* s = buf + src;
   u8* out = buf + t.dst;
-  qh_dl_head h;
-  u32 reason = (u32)qh_dl_header(s, size, &h);
-  if (!reason && (u64)h.total != count) reason = QH_PQ_R_DELTA_COUNT;
-  u64 pos = 0, carry = 0, produced = 0, sum = 0;   // sum (lengths): bytes of the values so far
-  if (!reason) {
-    pos = h.end;
-    if (count) {
-      carry = h.first; produced = 1;
-      if (lengths) {
-        if ((int)(u32)carry < 0) reason = QH_PQ_R_DELTA_LENGTH;
-        else if (lane == 0) { qh_pq_ent e; e.pos = 0; e.len = (u32)carry; e.pad = 0; ent[0] = e; }
-        sum = (u32)carry;
-      } else if (lane == 0) {
-        if (width == 4) ((u32*)out)[0] = (u32)carry; else ((u64*)out)[0] = carry;
+  u32 reason = QH_PQ_OK;
+  u64 begin = 0, pos = 0, sum = 0;   // begin: where this walk's stream begins behind src; sum (lengths): bytes of the values so far
+  const u32 walks = dba ? 2u : 1u;
+  for (u32 walk = 0; walk < walks && !reason; ++walk) {
+    const bool pre = dba && walk == 0, suf = dba && walk == 1, lens = lengths || suf;
+    begin += pos;
+    const u8* s = buf + src + begin;
+    const u64 ssize = size - begin;
+    qh_dl_head h;
+    reason = (u32)qh_dl_header(s, ssize, &h);
+    if (!reason && (u64)h.total != count) reason = QH_PQ_R_DELTA_COUNT;
+    u64 carry = 0, produced = 0;
+    u32 prev_len = 0;   // (suffix walk) the length of the value before the step
+    pos = 0; sum = 0;
+    if (!reason) {
+      pos = h.end;
+      if (count) {
+        carry = h.first; produced = 1;
+        if (pre) {
+          reason = (u32)qh_dba_check_prefix((u32)carry, true);
+          if (!reason && lane == 0) ent[0].pad = 0;
+        } else if (lens) {
+          if (suf) reason = (u32)qh_dba_check_value(0, (u32)carry, 0, width);
+          else if ((int)(u32)carry < 0) reason = QH_PQ_R_DELTA_LENGTH;
+          if (!reason && lane == 0) { qh_pq_ent e; e.pos = 0; e.len = (u32)carry; e.pad = 0; ent[0] = e; }
+          sum = (u32)carry; prev_len = (u32)carry;
+        } else if (lane == 0) {
+          if (width == 4) ((u32*)out)[0] = (u32)carry; else ((u64*)out)[0] = carry;
+        }
       }
     }
-  }
-  while (!reason && produced < count) {
-    u64 min_delta = 0, wat = 0, at = 0;
-    reason = (u32)qh_dl_block(s, size, pos, h.mpb, &min_delta, &wat, &at);
-    if (reason) break;
-    const u64 left = count - produced, in_block = left < (u64)h.block ? left : (u64)h.block;
-    const u64 mbytes = h.vpm >> 3;   // bytes of a miniblock per bit of width
-    u32 cur_m = 0, cur_w = s[wat];
-    reason = (u32)qh_dl_miniblock(cur_w, bits, h.vpm, size - at);
-    for (u64 k0 = 0; !reason && k0 < in_block; k0 += 64) {
-      const u64 last = k0 + 63 < in_block ? k0 + 63 : in_block - 1;
-      const u32 m_lo = (u32)(k0 / h.vpm), m_hi = (u32)(last / h.vpm);
-      if (m_lo != cur_m) {   // the step before ended with its miniblock
-        at += mbytes * cur_w; cur_m = m_lo; cur_w = s[wat + cur_m];
-        reason = (u32)qh_dl_miniblock(cur_w, bits, h.vpm, size - at);
-        if (reason) break;
+    while (!reason && produced < count) {
+      u64 min_delta = 0, wat = 0, at = 0;
+      reason = (u32)qh_dl_block(s, ssize, pos, h.mpb, &min_delta, &wat, &at);
+      if (reason) break;
+      const u64 left = count - produced, in_block = left < (u64)h.block ? left : (u64)h.block;
+      const u64 mbytes = h.vpm >> 3;   // bytes of a miniblock per bit of width
+      u32 cur_m = 0, cur_w = s[wat];
+      reason = (u32)qh_dl_miniblock(cur_w, bits, h.vpm, ssize - at);
+      for (u64 k0 = 0; !reason && k0 < in_block; k0 += 64) {
+        const u64 last = k0 + 63 < in_block ? k0 + 63 : in_block - 1;
+        const u32 m_lo = (u32)(k0 / h.vpm), m_hi = (u32)(last / h.vpm);
+        if (m_lo != cur_m) {   // the step before ended with its miniblock
+          at += mbytes * cur_w; cur_m = m_lo; cur_w = s[wat + cur_m];
+          reason = (u32)qh_dl_miniblock(cur_w, bits, h.vpm, ssize - at);
+          if (reason) break;
+        }
+        u64 next_at = 0;
+        u32 next_w = 0;
+        if (m_hi != m_lo) {
+          next_at = at + mbytes * cur_w; next_w = s[wat + m_hi];
+          reason = (u32)qh_dl_miniblock(next_w, bits, h.vpm, ssize - next_at);
+          if (reason) break;
+        }
+        const u64 v = k0 + (u64)lane;
+        const bool active = v <= last;
+        u64 x = 0;
+        if (active) {
+          const u32 mi = (u32)(v / h.vpm);
+          const u64 kk = v - (u64)mi * h.vpm;
+          x = (mi == m_lo ? qh_dl_extract(s + at, kk, cur_w) : qh_dl_extract(s + next_at, kk, next_w)) + min_delta;
+        }
+        const u64 val = carry + pq_incl_scan64(x, lane);
+        carry = pq_lane63(val);   // (an idle lane adds 0: lane 63 holds the step's last value)
+        if (pre) {
+          if (qh_ballot(active && qh_dba_check_prefix((u32)val, false))) { reason = QH_PQ_R_DBA_PREFIX; break; }
+          if (active) ent[produced + v].pad = (u32)val;
+        } else if (lens) {
+          const u32 len = (u32)val;   // (suffix walk: the suffix length)
+          u32 pfx = 0, full = len;
+          if (suf) {
+            if (active) pfx = ent[produced + v].pad;
+            full = pfx + len;
+            u32 before = (u32)__shfl_up((int)full, 1, 64);
+            if (lane == 0) before = prev_len;
+            const u32 bad = active ? (u32)qh_dba_check_value(pfx, len, before, width) : 0u;
+            const u64 who = qh_ballot(bad != 0);
+            if (who) { reason = qh_readlane32(bad, __builtin_ctzll(who)); break; }
+            prev_len = qh_readlane32(full, (int)(last - k0));
+          } else if (qh_ballot(active && (int)len < 0)) { reason = QH_PQ_R_DELTA_LENGTH; break; }
+          const u64 incl = pq_incl_scan64(active ? (u64)len : 0, lane);
+          if (active) { qh_pq_ent e; e.pos = sum + incl - len; e.len = full; e.pad = pfx; ent[produced + v] = e; }
+          sum += pq_lane63(incl);
+        } else if (active) {
+          if (width == 4) ((u32*)out)[produced + v] = (u32)val; else ((u64*)out)[produced + v] = val;
+        }
+        if (m_hi != m_lo) { at = next_at; cur_w = next_w; cur_m = m_hi; }
       }
-      u64 next_at = 0;
-      u32 next_w = 0;
-      if (m_hi != m_lo) {
-        next_at = at + mbytes * cur_w; next_w = s[wat + m_hi];
-        reason = (u32)qh_dl_miniblock(next_w, bits, h.vpm, size - next_at);
-        if (reason) break;
-      }
-      const u64 v = k0 + (u64)lane;
-      const bool active = v <= last;
-      u64 x = 0;
-      if (active) {
-        const u32 mi = (u32)(v / h.vpm);
-        const u64 kk = v - (u64)mi * h.vpm;
-        x = (mi == m_lo ? qh_dl_extract(s + at, kk, cur_w) : qh_dl_extract(s + next_at, kk, next_w)) + min_delta;
-      }
-      const u64 val = carry + pq_incl_scan64(x, lane);
-      carry = pq_lane63(val);   // (an idle lane adds 0: lane 63 holds the step's last value)
-      if (lengths) {
-        const u32 len = (u32)val;
-        if (qh_ballot(active && (int)len < 0)) { reason = QH_PQ_R_DELTA_LENGTH; break; }
-        const u64 incl = pq_incl_scan64(active ? (u64)len : 0, lane);
-        if (active) { qh_pq_ent e; e.pos = sum + incl - len; e.len = len; e.pad = 0; ent[produced + v] = e; }
-        sum += pq_lane63(incl);
-      } else if (active) {
-        if (width == 4) ((u32*)out)[produced + v] = (u32)val; else ((u64*)out)[produced + v] = val;
-      }
-      if (m_hi != m_lo) { at = next_at; cur_w = next_w; cur_m = m_hi; }
+      if (reason) break;
+      pos = at + mbytes * cur_w;   // (the last miniblock that holds a value is stored whole)
+      produced += in_block;
     }
-    if (reason) break;
-    pos = at + mbytes * cur_w;   // (the last miniblock that holds a value is stored whole)
-    produced += in_block;
-  }
-  if (!reason && lengths) {
-    if (sum > size - pos) reason = QH_PQ_R_DELTA_LENGTH;
-    else {
-      const u64 base = src + pos;
-      if (lane == 0) ent[0].pos = base;
-      for (u64 i = 1 + (u64)lane; i < count; i += 64) ent[i].pos += base;
+    if (!reason && lens) {
+      if (suf) reason = (u32)qh_dba_check_total(sum, ssize - pos);
+      else if (sum > ssize - pos) reason = QH_PQ_R_DELTA_LENGTH;
+      if (!reason) {
+        const u64 base = src + begin + pos;
+        if (lane == 0 && count) ent[0].pos = base;   // (a raw stream may hold no value: then it has no entry either)
+        for (u64 i = 1 + (u64)lane; i < count; i += 64) ent[i].pos += base;
+      }
     }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
   }
   if (lane == 0) {
     if (status) status[k] = reason;
-    if (ends) ends[k] = pos;
+    if (ends) ends[k] = begin + pos;
     if (reason && err) pq_report(err, t.page, reason);
+  }
+}
+
+__global__ __launch_bounds__(64) void k_pq_delta(u8* buf, const qh_pq_dstream* __restrict__ tab, u32 n, const qh_pq_page* __restrict__ pages,
+                                                 const qh_pq_col* __restrict__ cols, const qh_pq_state* __restrict__ state, u64* err, u32* status, u64* ends) {
+  pq_delta_body<false>(buf, tab, n, pages, cols, state, err, status, ends);
+}
+__global__ __launch_bounds__(64) void k_pq_delta_dba(u8* buf, const qh_pq_dstream* __restrict__ tab, u32 n, const qh_pq_page* __restrict__ pages,
+                                                     const qh_pq_col* __restrict__ cols, const qh_pq_state* __restrict__ state, u64* err, u32* status, u64* ends) {
+  pq_delta_body<true>(buf, tab, n, pages, cols, state, err, status, ends);
+}
+
+// The DELTA_BYTE_ARRAY switch, a Utf8 column that has such a page, behind the scan of its lengths into offsets: k_csv_copy_utf8
+// with a prefix. Row k's value is off[k + 1] - off[k] bytes long, of which the last (length - prefix[k]) lie in the page at
+// strpos[k]: they go to data[off[k] + prefix[k] ..), up to 64 by the row's own lane, longer ones by the whole wavefront. A row
+// of another page of the column has prefix 0 and is copied whole. The first prefix[k] bytes are k_pq_dba_fill's.
+__global__ __launch_bounds__(QH_BLOCK) void k_pq_dba_copy(const u8* __restrict__ buf, const u64* __restrict__ strpos, const u32* __restrict__ off,
+                                                          const u32* __restrict__ prefix, u64 nrows, u8* __restrict__ data) {
+  const u64 nwords = (nrows + 63) / 64;
+  const u64 wave_global = ((u64)blockIdx.x * QH_BLOCK + threadIdx.x) >> 6;
+  const u64 nwaves = ((u64)gridDim.x * QH_BLOCK) >> 6;
+  const int lane = qh_lane();
+  for (u64 j = wave_global; j < nwords; j += nwaves) {
+    const u64 k = j * 64 + lane;
+    u64 src = 0;
+    u32 dst = 0, len = 0;
+    if (k < nrows) {
+      const u32 p = prefix[k], whole = off[k + 1] - off[k];
+      src = strpos[k]; dst = off[k] + p; len = p < whole ? whole - p : 0u;   // (p <= whole was checked: the value is prefix + suffix)
+    }
+    if (len <= 64) for (u32 b = 0; b < len; ++b) data[dst + b] = buf[src + b];
+    u64 big = qh_ballot(len > 64);
+    while (big) {
+      const int l = __builtin_ctzll(big);
+      big &= big - 1;
+      const u64 s2 = qh_readlane64(src, l);
+      const u32 d2 = qh_readlane32(dst, l), n2 = qh_readlane32(len, l);
+      for (u32 b = lane; b < n2; b += 64) data[d2 + b] = buf[s2 + b];
+    }
+  }
+}
+
+// The DELTA_BYTE_ARRAY switch: the prefixes. One wavefront (a workgroup of its own) per page, 64 rows of it per step, lane =
+// row; the suffixes are in place. Byte j < prefix[r] of row r is byte j of the row before it, which took it from the row before
+// that unless it is one of its own suffix bytes: so it is byte j of the nearest earlier non-NULL row k with prefix[k] <= j, and
+// there a suffix byte. Inside a step that row is found with one ballot of "non-NULL and prefix <= j" and the highest set bit
+// below the lane (qh_dba_source_lane): at byte j the lanes with prefix <= j are read and the others written, so a step reads
+// nothing that it writes. Where no lane below qualifies, the byte is byte j of the last non-NULL row of the steps before, which
+// is complete by then: that load does read what this wavefront stored in an earlier step, from whichever lane, under the rule
+// k_pq_unsnap rests on, with its wavefront-scope fence per step. A step that holds a prefix above 64 bytes walks its rows in
+// order instead, the whole wavefront copying each row's prefix from the row before, 64 bytes per trip, a fence per row. NULL
+// rows are idle lanes and never a source; rows outside the page are idle too. Every prefix was checked by k_pq_delta against
+// the length of the value before it, and the page's first is 0, so every source lies in a row of the page.
+// Row space (off != NULL; a Utf8 column behind the host wait and k_pq_dba_copy): a job is the rows [first, first + n) of the
+// column, the steps aligned to its 64-row validity words; valid == NULL means every row is there. Value space (off == NULL; a
+// FIXED_LEN_BYTE_ARRAY page behind k_pq_delta, before the wait): a job's entries lie at data[first ..), value i goes to
+// data[out + i * width ..) and there are state[page].nonnull of them; each lane first copies its own suffix (at most 16 bytes)
+// from where its entry says, then the fill runs as above after a fence. A set err word means the entries may be half written:
+// the wavefront leaves.
+__device__ __forceinline__ u64 pq_shfl64(u64 v, int from) {
+  return ((u64)(u32)__shfl((int)(u32)(v >> 32), from, 64) << 32) | (u32)__shfl((int)(u32)v, from, 64);
+}
+__global__ __launch_bounds__(64) void k_pq_dba_fill(u8* data, const qh_pq_fill* __restrict__ jobs, u32 n, const u32* __restrict__ off, const u32* __restrict__ prefix,
+                                                    const u64* __restrict__ valid_words, const qh_pq_state* __restrict__ state, const u64* err) {
+  const u32 k = blockIdx.x;
+  if (k >= n) return;
+  const qh_pq_fill job = jobs[k];
+  const int lane = qh_lane();
+  const bool rows = off != nullptr;
+  u64 r_begin = 0, r_end = 0;
+  const qh_pq_ent* ent = nullptr;
+  if (rows) { r_begin = job.first; r_end = job.first + job.n; }
+  else {
+    if (__hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != ~0ULL) return;
+    r_end = state[job.page].nonnull;
+    ent = (const qh_pq_ent*)(data + job.first);
+  }
+  u64 before = 0;        // where the last non-NULL row of the steps before begins in data
+  bool have = false;
+  for (u64 t0 = r_begin & ~(u64)63; t0 < r_end; t0 += 64) {
+    const u64 r = t0 + (u64)lane;
+    bool valid = r >= r_begin && r < r_end;
+    if (valid && rows && valid_words) valid = (valid_words[t0 >> 6] >> lane) & 1ULL;
+    u32 p = 0;
+    u64 o = 0;
+    if (valid) {
+      if (rows) { p = prefix[r]; o = off[r]; }
+      else {
+        const qh_pq_ent e = ent[r];
+        p = e.pad; o = job.out + r * job.width;
+        for (u32 b = p; b < e.len; ++b) data[o + b] = data[e.pos + (b - p)];   // (e.len is the width: k_pq_delta checked it)
+      }
+    }
+    const u64 there = qh_ballot(valid);
+    if (!there) continue;
+    if (!rows) __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    if (qh_ballot(valid && p > QH_DBA_STEP_PREFIX)) {
+      u64 todo = there;
+      while (todo) {
+        const int l = __builtin_ctzll(todo);
+        todo &= todo - 1;
+        const u32 pl = qh_readlane32(p, l);
+        const u64 ol = qh_readlane64(o, l);
+        if (have) for (u32 b = lane; b < pl; b += 64) data[ol + b] = data[before + b];
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        before = ol; have = true;
+      }
+    } else {
+      for (u32 j = 0; qh_ballot(valid && p > j); ++j) {
+        const u64 m = qh_ballot(valid && p <= j);
+        const int sl = qh_dba_source_lane(m, lane);
+        const u64 so = pq_shfl64(o, sl < 0 ? lane : sl);
+        if (valid && p > j && (sl >= 0 || have)) data[o + j] = data[(sl >= 0 ? so : before) + j];
+      }
+      before = qh_readlane64(o, 63 - __builtin_clzll(there)); have = true;
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    }
   }
 }
 
 // ---------------------------------------------------------------- launchers
 void launch_pq_delta(uint8_t* buf, const qh_pq_dstream* tab, uint32_t n, const qh_pq_page* pages, const qh_pq_col* cols, const qh_pq_state* state, uint64_t* err,
-                     uint32_t* status, uint64_t* ends, hipStream_t s) {
+                     uint32_t* status, uint64_t* ends, uint32_t kinds, hipStream_t s) {
   if (!n) return;
-  hipLaunchKernelGGL(k_pq_delta, dim3(n), dim3(64), 0, s, (u8*)buf, tab, (u32)n, pages, cols, state, (u64*)err, (u32*)status, (u64*)ends);
+  if (kinds & 1u) hipLaunchKernelGGL(k_pq_delta, dim3(n), dim3(64), 0, s, (u8*)buf, tab, (u32)n, pages, cols, state, (u64*)err, (u32*)status, (u64*)ends);
+  if (kinds & 2u) hipLaunchKernelGGL(k_pq_delta_dba, dim3(n), dim3(64), 0, s, (u8*)buf, tab, (u32)n, pages, cols, state, (u64*)err, (u32*)status, (u64*)ends);
+}
+void launch_pq_dba_copy(const uint8_t* buf, const uint64_t* strpos, const uint32_t* offsets, const uint32_t* prefix, uint64_t nrows, uint8_t* data, hipStream_t s) {
+  if (!nrows) return;
+  uint64_t g = ((nrows + 63) / 64 * 64 + QH_BLOCK - 1) / QH_BLOCK;
+  if (g > 8192) g = 8192;
+  hipLaunchKernelGGL(k_pq_dba_copy, dim3((unsigned)g), dim3(QH_BLOCK), 0, s, (const u8*)buf, (const u64*)strpos, (const u32*)offsets, (const u32*)prefix, (u64)nrows,
+                     (u8*)data);
+}
+void launch_pq_dba_fill(uint8_t* data, const qh_pq_fill* jobs, uint32_t n, const uint32_t* off, const uint32_t* prefix, const uint64_t* valid, const qh_pq_state* state,
+                        const uint64_t* err, hipStream_t s) {
+  if (!n) return;
+  hipLaunchKernelGGL(k_pq_dba_fill, dim3(n), dim3(64), 0, s, (u8*)data, jobs, (u32)n, (const u32*)off, (const u32*)prefix, (const u64*)valid, state, (const u64*)err);
 }
 void launch_pq_values_ext(const uint8_t* buf, const qh_pq_page* pages, uint32_t npages, const qh_pq_col* cols, const qh_pq_state* state, uint64_t* err,
                           uint64_t* utf8_bytes, hipStream_t s) {

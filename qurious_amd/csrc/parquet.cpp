@@ -13,7 +13,10 @@
 // kernel of their own (k_pq_unzstd, a whole Zstandard frame decoder; the content checksum is not verified). The gzip switch
 // (qhip_ctx_set_parquet_gzip), a fourth independent one, adds GZIP chunks the same way (k_pq_ungzip, an inflate kernel; the
 // CRC32 is not verified). The lz4 switch (qhip_ctx_set_parquet_lz4), a fifth, adds LZ4_RAW and legacy LZ4 chunks (k_pq_unlz4,
-// one wavefront per bare block; Hadoop's frames are split on the host). Whatever lies outside makes the whole call answer QHIP_UNSUPPORTED with nothing
+// one wavefront per bare block; Hadoop's frames are split on the host). The DELTA_BYTE_ARRAY switch
+// (qhip_ctx_set_parquet_delta_byte_array), a sixth, adds data pages of that encoding in Utf8 columns and FIXED_LEN_BYTE_ARRAY
+// decimals: k_pq_delta_dba decodes their prefix and suffix lengths, k_pq_dba_fill reconstructs the prefixes 64 rows at a time.
+// Whatever lies outside makes the whole call answer QHIP_UNSUPPORTED with nothing
 // created, and the caller takes the host path, which then produces every error message.
 //
 // Passes, all on the context's stream:
@@ -24,11 +27,15 @@
 //  (k_pq_unlz4     the lz4 switch, a file with LZ4 pages only: one wavefront per block, into the unpack area)
 //   2 k_pq_levels   definition levels -> validity words, non-NULL count per page, NULL count per column
 //  (k_pq_delta     set 2, a file with DELTA_* pages only: one wavefront per page, into the decoded area or the column's entries)
+//  (k_pq_delta_dba the DELTA_BYTE_ARRAY switch, a file with such pages only: both length streams of a page -> its entries)
+//  (k_pq_dba_fill  the DELTA_BYTE_ARRAY switch, FIXED_LEN_BYTE_ARRAY pages of that encoding only: value space, into the decoded area)
 //   3 k_pq_strings  Utf8: the length chains of dictionary pages and PLAIN data pages -> (length, position) entries
 //   4 k_pq_values   values: bit-unpack, dictionary gather, scatter over NULLs; Utf8 rows get (length, position)
 //  (k_pq_values_ext set 2, a file with RLE Boolean, BYTE_STREAM_SPLIT or DELTA_* pages only: the same body for those pages)
 //                   -> the ONE host wait: first offender, NULL counts, Utf8 byte totals (they size the data buffers)
 //   5 Utf8          lengths scanned in place into offsets, k_csv_copy_utf8 moves the bytes (no wait: stream-ordered)
+//  (k_pq_dba_copy / k_pq_dba_fill  the DELTA_BYTE_ARRAY switch, Utf8 columns with such a page only: k_pq_dba_copy in
+//                   k_csv_copy_utf8's place moves the suffixes, k_pq_dba_fill, row space, fills in the prefixes; no wait)
 #include <hip/hip_runtime_api.h>
 #include <algorithm>
 
@@ -40,7 +47,8 @@
 namespace qhip {
 
 static_assert(sizeof(qh_pq_dstream) == 32, "the delta-table entry has the layout both compilers agree on");
-static_assert(sizeof(qh_pq_page) == 80 && sizeof(qh_pq_col) == 48 && sizeof(qh_pq_ent) == 16, "the Parquet descriptors have the layout both compilers agree on");
+static_assert(sizeof(qh_pq_fill) == 32, "the fill-table entry has the layout both compilers agree on");
+static_assert(sizeof(qh_pq_page) == 80 && sizeof(qh_pq_col) == 56 && sizeof(qh_pq_ent) == 16, "the Parquet descriptors have the layout both compilers agree on");
 static_assert(sizeof(qh_pq_unpack) == 32, "the unpack-table entry has the layout both compilers agree on");
 
 qhip_table* table_from_parquet(Ctx* ctx, const ArrowSchema* schema, const uint8_t* bytes, int64_t n_bytes, const int32_t* columns, int32_t n_columns,
@@ -76,7 +84,8 @@ qhip_table* table_from_parquet(Ctx* ctx, const ArrowSchema* schema, const uint8_
   // ---- footer and page walk (host, one header per page)
   qhip_pq::Plan plan;
   try {
-    plan = qhip_pq::plan_file(bytes, (uint64_t)n_bytes, &names, types, proj, ctx->parquet_format, ctx->parquet_encodings, ctx->parquet_codecs, ctx->parquet_gzip, ctx->parquet_lz4);
+    plan = qhip_pq::plan_file(bytes, (uint64_t)n_bytes, &names, types, proj, ctx->parquet_format, ctx->parquet_encodings, ctx->parquet_codecs, ctx->parquet_gzip, ctx->parquet_lz4,
+                              ctx->parquet_dba);
   } catch (const qhip_pq::PqNeedsHost& e) {
     fail(QHIP_UNSUPPORTED, qhip_pq::needs_host_text(e));
   }
@@ -98,8 +107,10 @@ qhip_table* table_from_parquet(Ctx* ctx, const ArrowSchema* schema, const uint8_
   for (float& ms : ctx->parquet_pass_ms) ms = 0;
   ctx->parquet_unpack_ms = 0;
   ctx->parquet_delta_ms = 0;
-  hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // ([6]: behind the unpack pass, [7]: behind the delta pass)
-  struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int k = 0; k < 8; ++k) if (e[k]) (void)hipEventDestroy(e[k]); } } ev_guard{ev};
+  ctx->parquet_fill_ms = 0;
+  // ([6]: behind the unpack pass, [7]: behind the delta pass, [8]: behind the fill of the FIXED_LEN_BYTE_ARRAY pages, [9]: in front of the fill of the Utf8 columns)
+  hipEvent_t ev[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int k = 0; k < 10; ++k) if (e[k]) (void)hipEventDestroy(e[k]); } } ev_guard{ev};
   auto mark = [&](int k) {
     if (!ctx->timing) return;
     if (!ev[k]) QHIP_HIP_CHECK(hipEventCreate(&ev[k]));
@@ -129,7 +140,7 @@ qhip_table* table_from_parquet(Ctx* ctx, const ArrowSchema* schema, const uint8_
   QHIP_HIP_CHECK(hipMemcpyAsync(st.ptr, st_host.data(), st.bytes, hipMemcpyHostToDevice, ctx->stream));
   uint64_t* st_dev = st.as<uint64_t>();
 
-  struct Out { DevColumn col; std::shared_ptr<DevBuf> strpos, ent; };
+  struct Out { DevColumn col; std::shared_ptr<DevBuf> strpos, ent, prefix; };
   std::vector<Out> outs(ncols);
   std::vector<qh_pq_col> desc(ncols);
   const size_t words = (size_t)((R + 63) / 64);
@@ -151,6 +162,11 @@ qhip_table* table_from_parquet(Ctx* ctx, const ArrowSchema* schema, const uint8_
       o.ent = std::make_shared<DevBuf>((size_t)(R + cp.dict_entries) * sizeof(qh_pq_ent));
       d.strpos = o.strpos->as<pq_u64>();
       d.ent = o.ent->as<qh_pq_ent>();
+      if (cp.dba) {   // (rows of the column's other pages keep prefix 0)
+        o.prefix = std::make_shared<DevBuf>((size_t)R * 4);
+        QHIP_HIP_CHECK(hipMemsetAsync(o.prefix->ptr, 0, (size_t)R * 4, ctx->stream));
+        d.prefix = o.prefix->as<pq_u32>();
+      }
     } else if (cp.boolean) {
       o.col.values = std::make_shared<DevBuf>(words * 8);   // bit-packed, whole 64-row words
       QHIP_HIP_CHECK(hipMemsetAsync(o.col.values->ptr, 0, words * 8, ctx->stream));
@@ -180,6 +196,14 @@ qhip_table* table_from_parquet(Ctx* ctx, const ArrowSchema* schema, const uint8_
   DevBuf delta_d;
   if (ndelta) delta_d.alloc((size_t)ndelta * sizeof(qh_pq_dstream));
   if (ndelta) QHIP_HIP_CHECK(hipMemcpyAsync(delta_d.ptr, plan.delta.data(), (size_t)ndelta * sizeof(qh_pq_dstream), hipMemcpyHostToDevice, ctx->stream));
+  // the DELTA_BYTE_ARRAY switch: the fill jobs of the FIXED_LEN_BYTE_ARRAY pages, behind them those of the Utf8 pages by column
+  std::stable_sort(plan.fill_rows.begin(), plan.fill_rows.end(), [](const qh_pq_fill& a, const qh_pq_fill& b) { return a.col < b.col; });
+  const uint32_t nfillv = (uint32_t)plan.fill_values.size(), nfillr = (uint32_t)plan.fill_rows.size(), ndba = nfillv + nfillr;
+  std::vector<qh_pq_fill> fill_host(plan.fill_values);
+  fill_host.insert(fill_host.end(), plan.fill_rows.begin(), plan.fill_rows.end());
+  DevBuf fill_d;
+  if (!fill_host.empty()) fill_d.alloc(fill_host.size() * sizeof(qh_pq_fill));
+  if (!fill_host.empty()) QHIP_HIP_CHECK(hipMemcpyAsync(fill_d.ptr, fill_host.data(), fill_host.size() * sizeof(qh_pq_fill), hipMemcpyHostToDevice, ctx->stream));
   mark(1);
 
   // ---- level 2: the Snappy pages into their slots; codec set 2: the ZSTD pages into theirs; the gzip switch: the GZIP pages; the lz4
@@ -196,8 +220,12 @@ qhip_table* table_from_parquet(Ctx* ctx, const ArrowSchema* schema, const uint8_
   mark(2);
   if (ndelta) {   // (behind the levels: a page's stream begins where they end and holds its non-NULL rows)
     launch_pq_delta(file.as<uint8_t>(), delta_d.as<qh_pq_dstream>(), ndelta, pages_d.as<qh_pq_page>(), cols_d.as<qh_pq_col>(), state_d.as<qh_pq_state>(), st_dev, nullptr,
-                    nullptr, ctx->stream);
+                    nullptr, (ndelta > ndba ? 1u : 0u) | (ndba ? 2u : 0u), ctx->stream);
     mark(7);
+    if (nfillv) {   // (the FIXED_LEN_BYTE_ARRAY pages of DELTA_BYTE_ARRAY: dense into their slots, from where k_pq_values_ext reads them as PLAIN)
+      launch_pq_dba_fill(file.as<uint8_t>(), fill_d.as<qh_pq_fill>(), nfillv, nullptr, nullptr, nullptr, state_d.as<qh_pq_state>(), st_dev, ctx->stream);
+      mark(8);
+    }
   }
   launch_pq_strings(file.as<uint8_t>(), buf_bytes, pages_d.as<qh_pq_page>(), npages, cols_d.as<qh_pq_col>(), state_d.as<qh_pq_state>(), st_dev, ctx->stream);
   mark(3);
@@ -230,7 +258,19 @@ qhip_table* table_from_parquet(Ctx* ctx, const ArrowSchema* schema, const uint8_
     o.col.data_bytes = (int64_t)total;
     uint32_t* off = o.col.values->as<uint32_t>();
     exclusive_scan_u32(off, off, R, off + R, ctx->stream);
-    launch_csv_copy_utf8(file.as<uint8_t>(), o.strpos->as<uint64_t>(), off, R, o.col.data->as<uint8_t>(), ctx->stream);
+    if (o.prefix) launch_pq_dba_copy(file.as<uint8_t>(), o.strpos->as<uint64_t>(), off, o.prefix->as<uint32_t>(), R, o.col.data->as<uint8_t>(), ctx->stream);
+    else launch_csv_copy_utf8(file.as<uint8_t>(), o.strpos->as<uint64_t>(), off, R, o.col.data->as<uint8_t>(), ctx->stream);
+  }
+  if (nfillr) {   // the Utf8 columns with DELTA_BYTE_ARRAY pages: their prefixes, in row space, straight into the column's data
+    mark(9);
+    for (uint32_t a = 0; a < nfillr;) {
+      uint32_t b = a;
+      while (b < nfillr && plan.fill_rows[b].col == plan.fill_rows[a].col) ++b;
+      Out& o = outs[plan.fill_rows[a].col];
+      launch_pq_dba_fill(o.col.data->as<uint8_t>(), fill_d.as<qh_pq_fill>() + nfillv + a, b - a, o.col.values->as<uint32_t>(), o.prefix->as<uint32_t>(),
+                         o.col.validity ? o.col.validity->as<uint64_t>() : nullptr, nullptr, nullptr, ctx->stream);
+      a = b;
+    }
   }
   mark(5);
   for (auto& o : outs) t->cols.push_back(std::move(o.col));
@@ -246,6 +286,16 @@ qhip_table* table_from_parquet(Ctx* ctx, const ArrowSchema* schema, const uint8_
     if (ev[7]) {   // ... and the "string walk" behind the delta pass
       (void)hipEventElapsedTime(&ctx->parquet_delta_ms, ev[2], ev[7]);
       (void)hipEventElapsedTime(&ctx->parquet_pass_ms[2], ev[7], ev[3]);
+    }
+    if (ev[8]) {   // ... behind the fill of the FIXED_LEN_BYTE_ARRAY pages, where there is one
+      (void)hipEventElapsedTime(&ctx->parquet_fill_ms, ev[7], ev[8]);
+      (void)hipEventElapsedTime(&ctx->parquet_pass_ms[2], ev[8], ev[3]);
+    }
+    if (ev[9]) {   // ... and "Utf8" ends in front of the fill of the Utf8 columns
+      float rows_ms = 0;
+      (void)hipEventElapsedTime(&rows_ms, ev[9], ev[5]);
+      (void)hipEventElapsedTime(&ctx->parquet_pass_ms[4], ev[4], ev[9]);
+      ctx->parquet_fill_ms += rows_ms;
     }
   }
   time_mark(ctx, 1);
@@ -377,7 +427,7 @@ void delta_decode(Ctx* ctx, const uint8_t* bytes, int64_t n_bytes, const int64_t
   hipEvent_t ev[2] = {nullptr, nullptr};
   struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int k = 0; k < 2; ++k) if (e[k]) (void)hipEventDestroy(e[k]); } } ev_guard{ev};
   if (ctx->timing) { QHIP_HIP_CHECK(hipEventCreate(&ev[0])); QHIP_HIP_CHECK(hipEventCreate(&ev[1])); QHIP_HIP_CHECK(hipEventRecord(ev[0], ctx->stream)); }
-  launch_pq_delta(buf.as<uint8_t>(), tab_d.as<qh_pq_dstream>(), nt, nullptr, nullptr, nullptr, nullptr, st_d.as<uint32_t>(), end_d.as<uint64_t>(), ctx->stream);
+  launch_pq_delta(buf.as<uint8_t>(), tab_d.as<qh_pq_dstream>(), nt, nullptr, nullptr, nullptr, nullptr, st_d.as<uint32_t>(), end_d.as<uint64_t>(), 1u, ctx->stream);
   if (ctx->timing) QHIP_HIP_CHECK(hipEventRecord(ev[1], ctx->stream));
   std::vector<uint8_t> dense((size_t)area);
   std::vector<uint32_t> st(nt);
@@ -395,6 +445,92 @@ void delta_decode(Ctx* ctx, const uint8_t* bytes, int64_t n_bytes, const int64_t
     if (!st[i] && nb) memcpy(out + at, dense.data() + (d.dst - base), (size_t)nb);
     at += nb;
   }
+}
+
+// qhip_parquet_dba_decode: raw DELTA_BYTE_ARRAY value streams through the kernels a file's pages go through: k_pq_delta_dba (both
+// length streams -> entries), then, behind a wait of its own that a file does not need (there the column's one wait serves), the
+// scan of the lengths on the host, k_pq_dba_copy and k_pq_dba_fill in row space, the values of the good streams one behind the
+// other as the rows of one column without NULLs. A refused stream is an answer (status), not an error.
+void dba_decode(Ctx* ctx, const uint8_t* bytes, int64_t n_bytes, const int64_t* src_offsets, const int32_t* widths, const int64_t* counts, int64_t n_streams,
+                uint8_t* out, int64_t out_bytes, int64_t* value_offsets, int64_t* total_bytes, int32_t* status) {
+  uint64_t nvalues = 0;
+  for (int64_t k = 0; k < n_streams; ++k) {
+    const int64_t a = src_offsets[k], b = src_offsets[k + 1];
+    if (a < 0 || b < a || b > n_bytes || b - a > 0x7FFFFFFF || counts[k] < 0 || counts[k] > 0x0FFFFFFF || widths[k] < 0 || widths[k] > 16)
+      fail(QHIP_INVALID_ARGUMENT, "qhip_parquet_dba_decode: stream " + std::to_string(k) + " lies outside the bytes, its count is negative or above 2^28 - 1, or its width is not 0 .. 16");
+    nvalues += (uint64_t)counts[k];
+  }
+  if (nvalues > 0x0FFFFFFFull) fail(QHIP_INVALID_ARGUMENT, "qhip_parquet_dba_decode: more than 2^28 - 1 values in all");
+  ctx->parquet_delta_ms = 0;
+  ctx->parquet_fill_ms = 0;
+  *total_bytes = 0;
+  if (!n_streams) return;
+  const uint64_t base = ((uint64_t)n_bytes + 15) & ~(uint64_t)15;
+  uint64_t area = 0;
+  std::vector<qh_pq_dstream> tab((size_t)n_streams);
+  for (int64_t k = 0; k < n_streams; ++k) {
+    qh_pq_dstream& d = tab[(size_t)k];
+    memset(&d, 0, sizeof d);
+    d.src = (uint64_t)src_offsets[k]; d.src_size = (uint32_t)(src_offsets[k + 1] - src_offsets[k]);
+    d.dst = base + area; d.count = (uint32_t)counts[k]; d.page = (uint32_t)k; d.width = (uint32_t)widths[k] | QH_PQ_DS_DBA;
+    area += (uint64_t)d.count * sizeof(qh_pq_ent);
+  }
+  QHIP_HIP_CHECK(hipSetDevice(ctx->device));
+  const uint32_t nt = (uint32_t)n_streams;
+  DevBuf buf((size_t)(base + area)), tab_d((size_t)nt * sizeof(qh_pq_dstream)), st_d((size_t)nt * 4);
+  if (n_bytes) QHIP_HIP_CHECK(hipMemcpyAsync(buf.ptr, bytes, (size_t)n_bytes, hipMemcpyHostToDevice, ctx->stream));
+  QHIP_HIP_CHECK(hipMemcpyAsync(tab_d.ptr, tab.data(), (size_t)nt * sizeof(qh_pq_dstream), hipMemcpyHostToDevice, ctx->stream));
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int k = 0; k < 4; ++k) if (e[k]) (void)hipEventDestroy(e[k]); } } ev_guard{ev};
+  if (ctx->timing) for (int k = 0; k < 4; ++k) QHIP_HIP_CHECK(hipEventCreate(&ev[k]));
+  if (ctx->timing) QHIP_HIP_CHECK(hipEventRecord(ev[0], ctx->stream));
+  launch_pq_delta(buf.as<uint8_t>(), tab_d.as<qh_pq_dstream>(), nt, nullptr, nullptr, nullptr, nullptr, st_d.as<uint32_t>(), nullptr, 2u, ctx->stream);
+  if (ctx->timing) QHIP_HIP_CHECK(hipEventRecord(ev[1], ctx->stream));
+  std::vector<qh_pq_ent> ents((size_t)(area / sizeof(qh_pq_ent)));
+  std::vector<uint32_t> st(nt);
+  if (area) QHIP_HIP_CHECK(hipMemcpyAsync(ents.data(), (const uint8_t*)buf.ptr + base, (size_t)area, hipMemcpyDeviceToHost, ctx->stream));
+  copy_sync(ctx->stream, st.data(), st_d.ptr, (size_t)nt * 4, hipMemcpyDeviceToHost);
+  if (ctx->timing) (void)hipEventElapsedTime(&ctx->parquet_delta_ms, ev[0], ev[1]);
+
+  // the good streams' values as rows: lengths into offsets, where the suffixes lie, the prefix lengths, a fill job per stream
+  std::vector<uint64_t> strpos;
+  std::vector<uint32_t> off(1, 0), prefix;
+  std::vector<qh_pq_fill> jobs;
+  uint64_t total = 0;
+  int64_t* vo = value_offsets;
+  for (uint32_t i = 0; i < nt; ++i) {
+    status[i] = (int32_t)st[i];
+    const qh_pq_ent* e = ents.data() + (tab[i].dst - base) / sizeof(qh_pq_ent);
+    const uint32_t c = st[i] ? 0u : tab[i].count;
+    if (c) {
+      qh_pq_fill fj;
+      memset(&fj, 0, sizeof fj);
+      fj.first = strpos.size(); fj.n = c; fj.page = i;
+      jobs.push_back(fj);
+    }
+    for (uint32_t v = 0; v <= tab[i].count; ++v) {
+      *vo++ = (int64_t)total;
+      if (v < c) {
+        total += e[v].len;
+        if (total > 0x7fffffffULL) fail(QHIP_INVALID_ARGUMENT, "qhip_parquet_dba_decode: the values exceed 2^31 - 1 bytes");
+        strpos.push_back(e[v].pos); prefix.push_back(e[v].pad); off.push_back((uint32_t)total);
+      }
+    }
+  }
+  *total_bytes = (int64_t)total;
+  const uint64_t rows = strpos.size();
+  if (!rows || !total || total > (uint64_t)out_bytes) return;
+  DevBuf pos_d((size_t)rows * 8), off_d((size_t)(rows + 1) * 4), pre_d((size_t)rows * 4), jobs_d(jobs.size() * sizeof(qh_pq_fill)), data_d((size_t)total);
+  QHIP_HIP_CHECK(hipMemcpyAsync(pos_d.ptr, strpos.data(), (size_t)rows * 8, hipMemcpyHostToDevice, ctx->stream));
+  QHIP_HIP_CHECK(hipMemcpyAsync(off_d.ptr, off.data(), (size_t)(rows + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
+  QHIP_HIP_CHECK(hipMemcpyAsync(pre_d.ptr, prefix.data(), (size_t)rows * 4, hipMemcpyHostToDevice, ctx->stream));
+  QHIP_HIP_CHECK(hipMemcpyAsync(jobs_d.ptr, jobs.data(), jobs.size() * sizeof(qh_pq_fill), hipMemcpyHostToDevice, ctx->stream));
+  launch_pq_dba_copy(buf.as<uint8_t>(), pos_d.as<uint64_t>(), off_d.as<uint32_t>(), pre_d.as<uint32_t>(), rows, data_d.as<uint8_t>(), ctx->stream);
+  if (ctx->timing) QHIP_HIP_CHECK(hipEventRecord(ev[2], ctx->stream));
+  launch_pq_dba_fill(data_d.as<uint8_t>(), jobs_d.as<qh_pq_fill>(), (uint32_t)jobs.size(), off_d.as<uint32_t>(), pre_d.as<uint32_t>(), nullptr, nullptr, nullptr, ctx->stream);
+  if (ctx->timing) QHIP_HIP_CHECK(hipEventRecord(ev[3], ctx->stream));
+  copy_sync(ctx->stream, out, data_d.ptr, (size_t)total, hipMemcpyDeviceToHost);
+  if (ctx->timing) (void)hipEventElapsedTime(&ctx->parquet_fill_ms, ev[2], ev[3]);
 }
 
 }  // namespace qhip
@@ -426,6 +562,22 @@ int qhip_ctx_parquet_delta_ms(const qhip_ctx* ctx, double* out) {
   if (!ctx || !out) return QHIP_INVALID_ARGUMENT;
   *out = (double)ctx->parquet_delta_ms;
   return QHIP_OK;
+}
+
+int qhip_ctx_parquet_fill_ms(const qhip_ctx* ctx, double* out) {
+  if (!ctx || !out) return QHIP_INVALID_ARGUMENT;
+  *out = (double)ctx->parquet_fill_ms;
+  return QHIP_OK;
+}
+
+int qhip_parquet_dba_decode(qhip_ctx* ctx, const void* bytes, int64_t n_bytes, const int64_t* src_offsets, const int32_t* widths, const int64_t* counts,
+                            int64_t n_streams, void* out, int64_t out_bytes, int64_t* value_offsets, int64_t* total_bytes, int32_t* status) {
+  if (!ctx || n_bytes < 0 || (n_bytes > 0 && !bytes) || n_streams < 0 || out_bytes < 0 || (out_bytes > 0 && !out) || !total_bytes) return QHIP_INVALID_ARGUMENT;
+  if (n_streams > 0 && (!src_offsets || !widths || !counts || !value_offsets || !status)) return QHIP_INVALID_ARGUMENT;
+  if (n_streams >= (1 << 24)) return QHIP_INVALID_ARGUMENT;
+  return guarded(ctx, [&] {
+    dba_decode(ctx, (const uint8_t*)bytes, n_bytes, src_offsets, widths, counts, n_streams, (uint8_t*)out, out_bytes, value_offsets, total_bytes, status);
+  });
 }
 
 int qhip_parquet_delta_decode(qhip_ctx* ctx, const void* bytes, int64_t n_bytes, const int64_t* src_offsets, const int32_t* widths, const int64_t* counts,

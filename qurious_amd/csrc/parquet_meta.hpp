@@ -5,7 +5,8 @@
 // chunks into an unpack table with their slots in the unpack area and, at encoding set 2, data pages V2 and the DELTA_* pages into
 // a delta table with their slots in the decoded area and, at codec set 2, the pages of ZSTD chunks into a second unpack table
 // with slots in the same unpack area and, with the gzip switch on, the pages of GZIP chunks into a third and, with the lz4
-// switch on, the blocks of LZ4_RAW and legacy LZ4 pages into a fourth. Plain C++, no Arrow, no HIP.
+// switch on, the blocks of LZ4_RAW and legacy LZ4 pages into a fourth and, with the DELTA_BYTE_ARRAY switch on, the pages of
+// that encoding into the delta table and a fill table. Plain C++, no Arrow, no HIP.
 // A ZSTD page's frame header and block headers are checked here (qh_zstd_check_frame) before anything is reserved; its content
 // checksum, where it has one, is skipped and not verified. A GZIP page's member header and ISIZE are checked here
 // (qh_gzip_check_member); its CRC32 is skipped and not verified either. An LZ4 page's size is checked against the 255x bound
@@ -21,6 +22,7 @@
 #include "device/qhip_parquet.inc"
 #include "device/qhip_snappy.inc"
 #include "device/qhip_delta.inc"
+#include "device/qhip_dba.inc"
 #include "device/qhip_zstd.inc"
 #include "device/qhip_inflate.inc"
 #include "device/qhip_lz4.inc"
@@ -38,8 +40,9 @@ static_assert(QH_PQ_R_GZIP_BASE == QH_PQ_R_ZSTD_OFFSET && QH_PQ_R_GZIP_MEMBER ==
               "the Gzip reasons follow the Zstd reasons and the decoder's error codes");
 
 static_assert(QH_PQ_R_LZ4_BASE == QH_PQ_R_GZIP_TRAILER && QH_PQ_R_LZ4_SIZE == QH_PQ_R_LZ4_BASE + QH_LZ4_E_SIZE &&
-                  QH_PQ_R_LZ4_END == QH_PQ_R_LZ4_BASE + QH_LZ4_E_END && QH_PQ_R_COUNT == QH_PQ_R_LZ4_BASE + QH_LZ4_E_COUNT,
+                  QH_PQ_R_LZ4_END == QH_PQ_R_LZ4_BASE + QH_LZ4_E_END && QH_PQ_R_DBA_PREFIX == QH_PQ_R_LZ4_BASE + QH_LZ4_E_COUNT,
               "the LZ4 reasons follow the Gzip reasons and the decoder's error codes");
+static_assert(QH_PQ_R_DBA_WIDTH == QH_PQ_R_DBA_PREFIX + 2 && QH_PQ_R_COUNT == QH_PQ_R_DBA_WIDTH + 1, "the DELTA_BYTE_ARRAY reasons follow the LZ4 reasons");
 
 namespace qhip_pq {
 
@@ -335,6 +338,7 @@ struct ColPlan {
   uint32_t phys = 0, flba = 0, width = 0, narrow = 0;
   bool optional = true, utf8 = false, boolean = false;
   uint64_t dict_entries = 0;   // Utf8: entries of all its dictionary pages
+  bool dba = false;            // Utf8: a DELTA_BYTE_ARRAY page among its pages (the column gets a per-row prefix array)
 };
 
 // does the file store Arrow type `a` in this leaf the way the device decodes? Fills the column's physical description.
@@ -400,6 +404,11 @@ struct Plan {
   std::vector<qh_pq_dstream> delta;
   uint64_t decoded_base = 0, decoded_bytes = 0;
   bool has_ext = false;
+  // the DELTA_BYTE_ARRAY switch: such a page is an entry of `delta` marked QH_PQ_DS_DBA and a job for k_pq_dba_fill. A
+  // FIXED_LEN_BYTE_ARRAY page (fill_values, value space, before the host wait) gets a slot in the decoded area: num_values x
+  // width bytes for its dense values, where k_pq_values_ext reads it as PLAIN (its enc is QH_PQ_ENC_DELTA), and behind them,
+  // 16-byte aligned, num_values x 16 bytes for its entries. A Utf8 page (fill_rows, row space, after the wait) needs no slot.
+  std::vector<qh_pq_fill> fill_values, fill_rows;
   uint64_t packed_bytes() const { return unpack.empty() && unzstd.empty() && ungzip.empty() && unlz4.empty() ? upload_bytes : unpack_base + unpack_bytes; }
   uint64_t buffer_bytes() const { return decoded_bytes ? decoded_base + decoded_bytes : packed_bytes(); }
 };
@@ -413,8 +422,11 @@ struct Plan {
 // (qhip_ctx_set_parquet_gzip); 1 admits GZIP chunks, whatever the other three say; at 0 nothing below differs. lz4: the lz4
 // switch (qhip_ctx_set_parquet_lz4); 1 admits LZ4_RAW chunks (codec 7: a page is one bare LZ4 block) and chunks of the legacy id
 // (codec 5: Hadoop's frames where they tile the page, one bare block otherwise), whatever the other four say; at 0 nothing differs.
+// dba: the DELTA_BYTE_ARRAY switch (qhip_ctx_set_parquet_delta_byte_array); 1 admits data pages of that encoding in Utf8 columns
+// and in the FIXED_LEN_BYTE_ARRAY decimals, whatever the other five say (a V2 page still needs encoding set 2, a compressed chunk
+// its codec's switch); at 0 nothing differs.
 inline Plan plan_file(const uint8_t* file, uint64_t n, const std::vector<std::string>* names, const std::vector<ArrowType>& types, const std::vector<int32_t>& proj,
-                      int level = 1, int encodings = 1, int codecs = 1, int gzip = 0, int lz4 = 0) {
+                      int level = 1, int encodings = 1, int codecs = 1, int gzip = 0, int lz4 = 0, int dba = 0) {
   const bool set2 = encodings >= 2;
   if (n >= 4 && memcmp(file, "PARE", 4) == 0) needs_host(QH_PQ_R_ENCRYPTED);
   if (n >= 4 && memcmp(file + n - 4, "PARE", 4) == 0) needs_host(QH_PQ_R_ENCRYPTED);
@@ -586,9 +598,33 @@ inline Plan plan_file(const uint8_t* file, uint64_t n, const std::vector<std::st
           else if (set2 && h.encoding == ENC_BYTE_STREAM_SPLIT && pw) pg.enc = QH_PQ_ENC_BSS;
           else if (set2 && h.encoding == ENC_DELTA_BINARY_PACKED && (ptype == PT_INT32 || ptype == PT_INT64)) pg.enc = QH_PQ_ENC_DELTA;
           else if (set2 && h.encoding == ENC_DELTA_LENGTH_BYTE_ARRAY && cp.utf8) pg.enc = QH_PQ_ENC_DELTA_LEN;
+          else if (dba >= 1 && h.encoding == ENC_DELTA_BYTE_ARRAY && cp.utf8) pg.enc = QH_PQ_ENC_DBA;
+          else if (dba >= 1 && h.encoding == ENC_DELTA_BYTE_ARRAY && cp.phys == QH_PQ_P_FLBA) pg.enc = QH_PQ_ENC_DELTA;   // (dense in its slot behind k_pq_dba_fill)
           else needs_host(QH_PQ_R_ENCODING, G, C, pageno);
           if (pg.enc >= QH_PQ_ENC_RLE_BOOL) plan.has_ext = true;
-          if (pg.enc == QH_PQ_ENC_DELTA || pg.enc == QH_PQ_ENC_DELTA_LEN) {
+          if (h.encoding == ENC_DELTA_BYTE_ARRAY) {
+            qh_pq_dstream d;
+            memset(&d, 0, sizeof d);
+            qh_pq_fill fj;
+            memset(&fj, 0, sizeof fj);
+            d.page = fj.page = (uint32_t)plan.pages.size();
+            d.width = cp.flba | QH_PQ_DS_DBA;
+            fj.n = (uint32_t)h.num_values; fj.col = (uint32_t)k;
+            if (cp.utf8) {
+              cp.dba = true;
+              fj.first = first_row + got;
+              plan.fill_rows.push_back(fj);
+            } else {
+              // (sized by the page's claim, which the row group's rows bound, as they bound the output columns)
+              fj.width = cp.flba;
+              fj.out = plan.decoded_bytes;
+              plan.decoded_bytes += ((uint64_t)h.num_values * cp.flba + 15) & ~(uint64_t)15;
+              fj.first = d.dst = plan.decoded_bytes;
+              plan.decoded_bytes += (uint64_t)h.num_values * sizeof(qh_pq_ent);
+              plan.fill_values.push_back(fj);
+            }
+            plan.delta.push_back(d);
+          } else if (pg.enc == QH_PQ_ENC_DELTA || pg.enc == QH_PQ_ENC_DELTA_LEN) {
             qh_pq_dstream d;
             memset(&d, 0, sizeof d);
             d.page = (uint32_t)plan.pages.size();
@@ -633,8 +669,11 @@ inline Plan plan_file(const uint8_t* file, uint64_t n, const std::vector<std::st
   // ---- ... and the decoded area behind that: a DELTA_BINARY_PACKED page's dict_pos is its slot
   if (plan.decoded_bytes) {
     plan.decoded_base = (plan.packed_bytes() + 15) & ~(uint64_t)15;
-    for (qh_pq_dstream& d : plan.delta)
-      if (!(d.width & QH_PQ_DS_LENGTHS)) { d.dst += plan.decoded_base; plan.pages[d.page].dict_pos = d.dst; }
+    for (qh_pq_dstream& d : plan.delta) {
+      if (d.width & QH_PQ_DS_DBA) { if (d.width & 0xFFu) d.dst += plan.decoded_base; }   // (its entries; a Utf8 page has the column's)
+      else if (!(d.width & QH_PQ_DS_LENGTHS)) { d.dst += plan.decoded_base; plan.pages[d.page].dict_pos = d.dst; }
+    }
+    for (qh_pq_fill& fj : plan.fill_values) { fj.first += plan.decoded_base; fj.out += plan.decoded_base; plan.pages[fj.page].dict_pos = fj.out; }
   }
   return plan;
 }

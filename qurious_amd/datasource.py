@@ -187,7 +187,10 @@ def read_parquet(path: str, columns: Optional[Sequence[str]] = None, batch_rows:
     Which page kinds and encodings are decoded is a second, independent switch, the encoding set
     (`Context.set_parquet_encodings` / QHIP_PARQUET_ENCODINGS). Set 1, the default: data pages V1 with PLAIN or dictionary
     values. Set 2 also decodes data pages V2 (`data_page_version="2.0"`), RLE Boolean values, BYTE_STREAM_SPLIT,
-    DELTA_BINARY_PACKED and DELTA_LENGTH_BYTE_ARRAY; DELTA_BYTE_ARRAY still takes the host path.
+    DELTA_BINARY_PACKED and DELTA_LENGTH_BYTE_ARRAY. DELTA_BYTE_ARRAY takes the host path unless the DELTA_BYTE_ARRAY switch
+    (`Context.set_parquet_delta_byte_array` / QHIP_PARQUET_DBA), a sixth independent one, is on: then such pages of Utf8 columns
+    and of FIXED_LEN_BYTE_ARRAY decimals are decoded on the device (a page whose first prefix length is not 0 still takes the
+    host path).
     Every other file falls back silently to the host read below, which also produces every error message."""
     import os
     import pyarrow.parquet as pq

@@ -276,6 +276,22 @@ extern "C" {
         out_bytes: i64,
         status: *mut i32,
     ) -> c_int;
+    pub fn qhip_ctx_set_parquet_delta_byte_array(ctx: *mut qhip_ctx, on: i32) -> c_int;
+    pub fn qhip_ctx_parquet_fill_ms(ctx: *const qhip_ctx, out: *mut f64) -> c_int;
+    pub fn qhip_parquet_dba_decode(
+        ctx: *mut qhip_ctx,
+        bytes: *const c_void,
+        n_bytes: i64,
+        src_offsets: *const i64,
+        widths: *const i32,
+        counts: *const i64,
+        n_streams: i64,
+        out: *mut c_void,
+        out_bytes: i64,
+        value_offsets: *mut i64,
+        total_bytes: *mut i64,
+        status: *mut i32,
+    ) -> c_int;
     pub fn qhip_ctx_parquet_delta_ms(ctx: *const qhip_ctx, out: *mut f64) -> c_int;
     pub fn qhip_table_to_arrow(
         ctx: *mut qhip_ctx,

@@ -28,8 +28,14 @@ DELTA_BINARY_PACKED integers and dates and DELTA_LENGTH_BYTE_ARRAY strings, or w
 encoding set 2 (Context.set_parquet_encodings). (d) then also has the delta pass (k_pq_delta, between k_pq_levels and
 k_pq_strings); the time of k_pq_values includes k_pq_values_ext, which runs right behind it.
 
+--encoding dba writes without dictionaries, data pages V2 whatever --page-version says, DELTA_BYTE_ARRAY for the Utf8 and decimal
+columns (what arrow-rs falls back to at writer version 2) and PLAIN for the rest, and sets the DELTA_BYTE_ARRAY switch
+(Context.set_parquet_delta_byte_array) and encoding set 2. (d) then has the delta pass (k_pq_delta_dba: both length streams of
+every such page) and, on a line of its own, the fill pass (k_pq_dba_fill: the decimal pages in front of the host wait, the Utf8
+columns behind it); "Utf8" is then the offset scans and k_pq_dba_copy.
+
     python tools/parquet_decode_timing.py [--gb 1.0] [--runs 10] [--warmup 2] [--repeat 2] [--threads 16] [--columns l_quantity,l_shipdate]
-                                          [--compression none|snappy|zstd|gzip|lz4] [--page-version 1.0|2.0] [--encoding plain|delta|bss]
+                                          [--compression none|snappy|zstd|gzip|lz4] [--page-version 1.0|2.0] [--encoding plain|delta|bss|dba]
 """
 import argparse
 import ctypes as C
@@ -60,6 +66,9 @@ def writer_options(schema, page_version, encoding):
     if encoding == "delta":
         kw["column_encoding"] = {f.name: "DELTA_LENGTH_BYTE_ARRAY" if pa.types.is_string(f.type) else "DELTA_BINARY_PACKED" for f in schema
                                  if pa.types.is_string(f.type) or pa.types.is_integer(f.type) or pa.types.is_date32(f.type)}
+    if encoding == "dba":
+        kw["data_page_version"] = "2.0"
+        kw["column_encoding"] = {f.name: "DELTA_BYTE_ARRAY" for f in schema if pa.types.is_string(f.type) or pa.types.is_decimal(f.type)}
     if encoding == "bss":
         kw["column_encoding"] = {f.name: "BYTE_STREAM_SPLIT" for f in schema
                                  if pa.types.is_integer(f.type) or pa.types.is_floating(f.type) or pa.types.is_decimal(f.type) or pa.types.is_date32(f.type)}
@@ -116,7 +125,8 @@ def main():
     ap.add_argument("--compression", choices=["none", "snappy", "zstd", "gzip", "lz4"], default="none",
                     help="snappy: pyarrow's defaults, decoded at format level 2; zstd: decoded at codec set 2; gzip / lz4: decoded with the gzip / lz4 switch on")
     ap.add_argument("--page-version", choices=["1.0", "2.0"], default="1.0", help="2.0: data pages V2, decoded at encoding set 2")
-    ap.add_argument("--encoding", choices=["plain", "delta", "bss"], default=None, help="no dictionaries; delta and bss are decoded at encoding set 2")
+    ap.add_argument("--encoding", choices=["plain", "delta", "bss", "dba"], default=None,
+                    help="no dictionaries; delta and bss are decoded at encoding set 2, dba (data pages V2) with the DELTA_BYTE_ARRAY switch on as well")
     args = ap.parse_args()
     pa.set_cpu_count(args.threads)
     columns = [c for c in args.columns.split(",") if c] or None
@@ -129,6 +139,9 @@ def main():
         ctx.set_parquet_gzip(1)
     if args.compression == "lz4":
         ctx.set_parquet_lz4(1)
+    if args.encoding == "dba":
+        args.page_version = "2.0"
+        ctx.set_parquet_delta_byte_array(1)
     if args.page_version == "2.0" or args.encoding in ("delta", "bss"):
         ctx.set_parquet_encodings(2)
     hip = C.CDLL(None)   # (libqhip.so is loaded globally and brings the HIP runtime with it)
@@ -176,7 +189,7 @@ def main():
         per = []
         for _ in range(args.warmup + args.runs):
             device_path()
-            per.append(ctx.parquet_pass_ms() + [ctx.parquet_unpack_ms(), ctx.parquet_delta_ms()])
+            per.append(ctx.parquet_pass_ms() + [ctx.parquet_unpack_ms(), ctx.parquet_delta_ms(), ctx.parquet_fill_ms()])
         ctx.set_timing(False)
         per = per[args.warmup:]
         kernels = 0.0
@@ -188,10 +201,14 @@ def main():
                 med = statistics.median(p[5] for p in per)
                 kernels += med
                 print(f"(d) { {'snappy': 'k_pq_unsnap', 'zstd': 'k_pq_unzstd', 'gzip': 'k_pq_ungzip', 'lz4': 'k_pq_unlz4'}[args.compression] + ' (unpack)':32s} {med:9.3f} ms  {plain_bytes / max(med, 1e-6) / 1e6:9.1f} GB/s of uncompressed bytes", flush=True)
-            if k == 1 and args.encoding == "delta":
+            if k == 1 and args.encoding in ("delta", "dba"):
                 med = statistics.median(p[6] for p in per)
                 kernels += med
-                print(f"(d) {'k_pq_delta':32s} {med:9.3f} ms  {chunk_bytes / max(med, 1e-6) / 1e6:9.1f} GB/s of chunk bytes", flush=True)
+                print(f"(d) {'k_pq_delta_dba' if args.encoding == 'dba' else 'k_pq_delta':32s} {med:9.3f} ms  {chunk_bytes / max(med, 1e-6) / 1e6:9.1f} GB/s of chunk bytes", flush=True)
+            if k == 4 and args.encoding == "dba":
+                med = statistics.median(p[7] for p in per)
+                kernels += med
+                print(f"(d) {'k_pq_dba_fill (both places)':32s} {med:9.3f} ms  {chunk_bytes / max(med, 1e-6) / 1e6:9.1f} GB/s of chunk bytes", flush=True)
         print(f"(d) kernels together (all but the upload) {kernels:9.3f} ms  {chunk_bytes / max(kernels, 1e-6) / 1e6:9.1f} GB/s of chunk bytes", flush=True)
         del src
         m.close()
