@@ -324,6 +324,21 @@ int qhip_ctx_csv_pass_ms(const qhip_ctx* ctx, double* out, int32_t n_out);
  * Boolean / Timestamp columns, decoded by kernels of their own — level 1 launches what it always launched. The environment's
  * QHIP_CSV_GRAMMAR (1 / 2) is read when the context is created. */
 int qhip_ctx_set_csv_grammar(qhip_ctx* ctx, int32_t level);
+/* What qhip_table_from_csv (at either grammar level) and qhip_table_from_json decode in a float column. level 1 (the default):
+ * Float64 only, and only spellings in Clinger's exact range — the digits form an integer <= 2^53, the effective |power of ten| is
+ * <= 22; one 17-digit value sends the file to the host, and so does a Float32 column. level 2: every spelling of
+ * -?[0-9]+(.[0-9]+)?([eE][-+]?[0-9]+)? with any number of digits, converted on the device to the nearest Float64 (ties to even,
+ * subnormal results included; csrc/device/qhip_float.inc, the Eisel-Lemire algorithm), and Float32 columns, converted from the
+ * decimal itself to the nearest Float32, as Arrow does — never by way of a double. A decimal that is zero keeps its sign.
+ * What stays on the host at level 2 (QHIP_UNSUPPORTED, reason "a float outside the exactly convertible spellings"):
+ *   - more than 19 significant digits when the first 19 do not settle the result: the value is converted from the 19-digit
+ *     truncation m and from m + 1, and only when both give the same bits is that the answer (a correctly rounded long spelling
+ *     of a binary value, such as the 55 digits of 0.1, passes; a true near-halfway case needs all its digits);
+ *   - a nonzero value that rounds to infinity or to zero (1e400, 2e-324; Arrow's CSV and JSON readers treat them differently);
+ *   - the lenient spellings: a leading '+', ".5", "5.", inf, nan, hex floats, surrounding blanks; in JSON also leading zeros.
+ * At level 1 nothing differs from a library without this switch. The environment's QHIP_FLOAT_PARSE (1 / 2) is read when the
+ * context is created. */
+int qhip_ctx_set_float_parse(qhip_ctx* ctx, int32_t level);
 /* Decode a file of newline-delimited JSON ON THE DEVICE into a table (csrc/json.cpp; replaces
  * datasource/file/json.rs + the upload). bytes: the file's contents in host memory, read only during the call. schema: a struct
  * ArrowSchema naming EVERY key a record may hold, with its type. columns / n_columns: the fields to decode, in output order

@@ -45,6 +45,9 @@ class Context {
   int64_t wide_key_joins() const { return qhip_ctx_wide_key_joins(ctx_); }
   // the device CSV decoder's grammar (qhip.h: 1 plain fields only, 2 also quoted fields, Boolean and Timestamp columns)
   void set_csv_grammar(int level) const { check(qhip_ctx_set_csv_grammar(ctx_, level)); }
+  // what the device CSV and JSON decoders parse in a float column (qhip.h: 1 Float64 in Clinger's exact range only, 2 every
+  // spelling, correctly rounded, and Float32 columns)
+  void set_float_parse(int level) const { check(qhip_ctx_set_float_parse(ctx_, level)); }
   // the device Parquet decoder's format level (qhip.h: 1 uncompressed chunks only, 2 also Snappy chunks)
   void set_parquet_format(int level) const { check(qhip_ctx_set_parquet_format(ctx_, level)); }
   // the device Parquet decoder's encoding set (qhip.h: 1 pages V1 with PLAIN or dictionary values, 2 also pages V2, RLE Booleans,

@@ -142,6 +142,7 @@ def load_library() -> C.CDLL:
             "qhip_ctx_wide_key_aggregates": (i64, [vp]),
             "qhip_ctx_set_wide_join_keys": (C.c_int, [vp, i32]),
             "qhip_ctx_set_csv_grammar": (C.c_int, [vp, i32]),
+            "qhip_ctx_set_float_parse": (C.c_int, [vp, i32]),
             "qhip_ctx_wide_key_joins": (i64, [vp]),
             "qhip_ctx_allow_deferred_sizes": (C.c_int, [vp, i32]),
             "qhip_ctx_forget_plans": (C.c_int, [vp]),
@@ -287,6 +288,12 @@ class Context:
         """The device CSV decoder's grammar: 1 (the default) plain fields only, any quote byte needs the host; 2 also canonical
         quoted fields, Boolean and Timestamp columns. QHIP_CSV_GRAMMAR sets it when the context is made."""
         self.check(self.lib.qhip_ctx_set_csv_grammar(self.handle, int(level)))
+
+    def set_float_parse(self, level: int):
+        """What the device CSV and JSON decoders parse in a float column: 1 (the default) Float64 spellings in Clinger's exact
+        range only (a 17-digit value needs the host), Float32 columns refused; 2 every spelling of the strict grammar, correctly
+        rounded on the device, and Float32 columns. QHIP_FLOAT_PARSE sets it when the context is made."""
+        self.check(self.lib.qhip_ctx_set_float_parse(self.handle, int(level)))
 
     def csv_pass_ms(self) -> List[float]:
         """Device time (ms) of the last device CSV decode's passes: upload, scan, record starts, decode, Utf8 (timing on)."""

@@ -345,6 +345,10 @@ struct Ctx {
   // the device CSV decoder's grammar level (csv.cpp): 1 = plain fields only, 2 = + canonical quoted fields, Boolean, Timestamp;
   // QHIP_CSV_GRAMMAR at context creation, qhip_ctx_set_csv_grammar later
   int csv_grammar = 1;
+  // what the device CSV and JSON decoders parse in a float column (csv.cpp, json.cpp; device/qhip_float.inc): 1 = Float64 in
+  // Clinger's exact range only, Float32 refused; 2 = every spelling of the strict grammar, correctly rounded, and Float32 columns;
+  // QHIP_FLOAT_PARSE at context creation, qhip_ctx_set_float_parse later
+  int float_parse = 1;
   // (total_out: the output table's own host word — the page-locked slot is part of a ring and is reused by later joins, so
   // the verified total is copied where the table can still find it however long it stays unsettled)
   struct PendingSize { uint32_t* slot; uint64_t key; uint64_t capacity; uint64_t dup_hint; std::shared_ptr<uint64_t> total_out; };

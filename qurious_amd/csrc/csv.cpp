@@ -31,8 +31,9 @@ static std::string needs_host(unsigned reason, uint64_t record) {
 
 static bool is_timestamp(const DType& t) { return t.id >= QHIP_TIMESTAMP_S && t.id <= QHIP_TIMESTAMP_NS; }
 
-static bool csv_decodable(const DType& t, int grammar) {
+static bool csv_decodable(const DType& t, int grammar, int float_parse) {
   if (dtype_is_integer(t)) return true;
+  if (float_parse >= 2 && t.id == QHIP_FLOAT32) return true;
   if (grammar >= 2 && (t.id == QHIP_BOOL || is_timestamp(t))) return true;   // (a zoned Timestamp never gets here: dtype_from_format refuses it)
   if (t.id == QHIP_DECIMAL128) return t.scale >= 0 && t.precision >= 1 && t.precision <= 38 && t.scale <= 38;
   return t.id == QHIP_FLOAT64 || t.id == QHIP_DATE32 || t.id == QHIP_UTF8;
@@ -66,7 +67,7 @@ qhip_table* table_from_csv(Ctx* ctx, const ArrowSchema* schema, const uint8_t* b
   for (int32_t c : proj) {
     if (c < 0 || c >= nfields) fail(QHIP_INVALID_ARGUMENT, "qhip_table_from_csv: projected column " + std::to_string(c) + " is not in the schema");
     const DType t = dtype_from_format(schema->children[c]->format);   // (unknown formats: QHIP_UNSUPPORTED)
-    if (!csv_decodable(t, grammar)) fail(QHIP_UNSUPPORTED, "CSV needs the host path: column type " + dtype_name(t) + " is not decoded on the device");
+    if (!csv_decodable(t, grammar, ctx->float_parse)) fail(QHIP_UNSUPPORTED, "CSV needs the host path: column type " + dtype_name(t) + " is not decoded on the device");
     types.push_back(t);
   }
 
@@ -191,7 +192,8 @@ qhip_table* table_from_csv(Ctx* ctx, const ArrowSchema* schema, const uint8_t* b
         d.width = (uint8_t)w;
         if (dtype_is_integer(ty)) { d.kind = QH_CSV_K_INT; d.a = dtype_is_signed(ty) ? 1 : 0; }
         else if (ty.id == QHIP_DATE32) d.kind = QH_CSV_K_DATE32;
-        else if (ty.id == QHIP_FLOAT64) d.kind = QH_CSV_K_FLOAT64;
+        else if (ty.id == QHIP_FLOAT64) d.kind = ctx->float_parse >= 2 ? QH_CSV_K_FLOAT64_FULL : QH_CSV_K_FLOAT64;   // (qhip_ctx_set_float_parse)
+        else if (ty.id == QHIP_FLOAT32) d.kind = QH_CSV_K_FLOAT32;
         else if (is_timestamp(ty)) { d.kind = QH_CSV_K_TIMESTAMP; d.a = (uint8_t)(3 * (ty.id - QHIP_TIMESTAMP_S)); }
         else { d.kind = QH_CSV_K_DECIMAL128; d.a = (uint8_t)ty.precision; d.b = (uint8_t)ty.scale; }
       }

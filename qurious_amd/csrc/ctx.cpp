@@ -350,6 +350,7 @@ int qhip_ctx_create(int device_index, qhip_ctx** out) {
     c->status.alloc(4 * QS_WORDS * sizeof(uint32_t));   // (a hash join uses three blocks: build status, probe status, pair total)
     c->timing = env_int("QHIP_TIMING", 0) != 0;
     c->csv_grammar = env_int("QHIP_CSV_GRAMMAR", 1) == 2 ? 2 : 1;
+    c->float_parse = env_int("QHIP_FLOAT_PARSE", 1) == 2 ? 2 : 1;
     c->parquet_format = env_int("QHIP_PARQUET_FORMAT", 1) == 2 ? 2 : 1;
     c->parquet_encodings = env_int("QHIP_PARQUET_ENCODINGS", 1) == 2 ? 2 : 1;
     c->parquet_codecs = env_int("QHIP_PARQUET_CODECS", 1) == 2 ? 2 : 1;
@@ -423,6 +424,12 @@ int64_t qhip_ctx_wide_key_joins(qhip_ctx* ctx) { return ctx ? ctx->wide_key_join
 int qhip_ctx_set_csv_grammar(qhip_ctx* ctx, int32_t level) {
   if (!ctx || level < 1 || level > 2) return QHIP_INVALID_ARGUMENT;
   ctx->csv_grammar = level;
+  return QHIP_OK;
+}
+
+int qhip_ctx_set_float_parse(qhip_ctx* ctx, int32_t level) {
+  if (!ctx || level < 1 || level > 2) return QHIP_INVALID_ARGUMENT;
+  ctx->float_parse = level;
   return QHIP_OK;
 }
 

@@ -4,7 +4,8 @@
 // the whole call answers QHIP_UNSUPPORTED: the device path never imitates a lenient spelling or an error message.
 //
 // One text for two compilers: included by kernels_csv.hip for hipcc and, as plain host C++, by tests/cpp/csv_tests.cpp, so the
-// functions the kernels call are the functions the CPU tests check. Self-contained: builtin integer types only, no #include.
+// functions the kernels call are the functions the CPU tests check. Self-contained: builtin integer types only, no #include but
+// qhip_float.inc beside it (the float_parse switch: every Float64 spelling, Float32).
 // Every function reads exactly the bytes [p, p + len) it is given (generic pointers: LDS or global memory on the device).
 #if defined(__HIP__) || defined(__HIPCC_RTC__)
 #define QH_CSV_HD __host__ __device__
@@ -68,6 +69,8 @@ QH_CSV_HD inline unsigned qh_csv_byte_class(unsigned char b, int quote) {
 #define QH_CSV_K_UTF8 4
 #define QH_CSV_K_BOOL 5          // grammar level 2: no `values` store per row, the kernel packs 64 rows into one ballot word
 #define QH_CSV_K_TIMESTAMP 6     // grammar level 2: a = fraction digits of the unit (0 s, 3 ms, 6 us, 9 ns)
+#define QH_CSV_K_FLOAT64_FULL 7  // float_parse level 2 (qhip_ctx_set_float_parse): every spelling of the grammar, qhip_float.inc
+#define QH_CSV_K_FLOAT32 8       // float_parse level 2: 4-byte values
 struct qh_csv_col {
   void* values;                  // row-indexed values of `width` bytes; Utf8: the u32 LENGTH of every row (scanned into offsets later)
   unsigned long long* valid;     // one ballot word per 64 rows (written by the kernel, not by the functions below)
@@ -231,6 +234,9 @@ QH_CSV_HD inline int qh_csv_parse_float64(const unsigned char* p, unsigned long 
   return QH_CSV_OK;
 }
 
+// ---- float_parse level 2: qh_parse_float64_full, qh_parse_float32_full
+#include "qhip_float.inc"
+
 // ---- Utf8: the bytes as they are (a NUL byte is data); well-formed UTF-8 only (no overlong forms, no surrogates, <= U+10FFFF)
 QH_CSV_HD inline int qh_csv_check_utf8(const unsigned char* p, unsigned long long len) {
   unsigned long long i = 0;
@@ -290,6 +296,18 @@ QH_CSV_HD inline int qh_csv_parse_store(const qh_csv_col& c, const unsigned char
       double v = 0.0;
       const int st = qh_csv_parse_float64(p, len, &v);
       ((double*)c.values)[row] = st == QH_CSV_OK ? v : 0.0;
+      return st;
+    }
+    case QH_CSV_K_FLOAT64_FULL: {
+      double v = 0.0;
+      const int st = qh_parse_float64_full(p, len, &v);
+      ((double*)c.values)[row] = st == QH_CSV_OK ? v : 0.0;
+      return st;
+    }
+    case QH_CSV_K_FLOAT32: {
+      float v = 0.0f;
+      const int st = qh_parse_float32_full(p, len, &v);
+      ((float*)c.values)[row] = st == QH_CSV_OK ? v : 0.0f;
       return st;
     }
     default: {   // QH_CSV_K_UTF8: an empty field is the empty string, never NULL
@@ -394,7 +412,7 @@ QH_CSV_HD inline int qh_csv_kind_reason(int kind) {
     case QH_CSV_K_INT: return QH_CSV_R_INT;
     case QH_CSV_K_DATE32: return QH_CSV_R_DATE;
     case QH_CSV_K_DECIMAL128: return QH_CSV_R_DECIMAL;
-    case QH_CSV_K_FLOAT64: return QH_CSV_R_FLOAT;
+    case QH_CSV_K_FLOAT64: case QH_CSV_K_FLOAT64_FULL: case QH_CSV_K_FLOAT32: return QH_CSV_R_FLOAT;
     case QH_CSV_K_BOOL: return QH_CSV_R_BOOL;
     case QH_CSV_K_TIMESTAMP: return QH_CSV_R_TIMESTAMP;
     default: return QH_CSV_R_UTF8;

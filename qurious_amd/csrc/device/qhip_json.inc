@@ -125,7 +125,8 @@ QH_CSV_HD inline void qh_json_store_null(const qh_json_field& fd, const qh_json_
     case QH_CSV_K_INT: qh_json_store_int(o.values, row, fd.b, 0ULL); break;
     case QH_CSV_K_DATE32: ((int*)o.values)[row] = 0; break;
     case QH_CSV_K_DECIMAL128: ((unsigned long long*)o.values)[2 * row] = 0; ((unsigned long long*)o.values)[2 * row + 1] = 0; break;
-    case QH_CSV_K_FLOAT64: case QH_CSV_K_TIMESTAMP: ((unsigned long long*)o.values)[row] = 0; break;
+    case QH_CSV_K_FLOAT64: case QH_CSV_K_FLOAT64_FULL: case QH_CSV_K_TIMESTAMP: ((unsigned long long*)o.values)[row] = 0; break;
+    case QH_CSV_K_FLOAT32: ((unsigned*)o.values)[row] = 0u; break;
     case QH_CSV_K_UTF8: ((unsigned*)o.values)[row] = 0u; o.strpos[row] = 0ULL; break;
     default: break;   // Boolean: the kernel packs the words
   }
@@ -261,6 +262,14 @@ QH_CSV_HD inline int qh_json_decode_record(const qh_json_desc& d, unsigned nfiel
             double v = 0.0;
             if (qh_json_leading_zero(t, tl) || qh_csv_parse_float64(t, tl, &v) != QH_CSV_OK) return QH_JSON_R_FLOAT;
             if (col >= 0) { ((double*)d.out[col].values)[row] = v; vm |= 1ULL << col; }
+          } else if (fd.kind == QH_CSV_K_FLOAT64_FULL) {
+            unsigned long long v = 0;
+            if (qh_json_leading_zero(t, tl) || qh_float_parse<false>(t, tl, true, &v) != QH_CSV_OK) return QH_JSON_R_FLOAT;
+            if (col >= 0) { ((unsigned long long*)d.out[col].values)[row] = v; vm |= 1ULL << col; }
+          } else if (fd.kind == QH_CSV_K_FLOAT32) {
+            unsigned long long v = 0;
+            if (qh_json_leading_zero(t, tl) || qh_float_parse<true>(t, tl, true, &v) != QH_CSV_OK) return QH_JSON_R_FLOAT;
+            if (col >= 0) { ((unsigned*)d.out[col].values)[row] = (unsigned)v; vm |= 1ULL << col; }
           } else if (fd.kind == QH_CSV_K_DECIMAL128) {
             // a JSON number without exponent: a digit on both sides of the point (the CSV grammar also takes ".5" and "5.")
             unsigned long long v[2] = {0, 0};

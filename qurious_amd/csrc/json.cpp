@@ -31,7 +31,8 @@ static std::string json_needs_host(unsigned reason, uint64_t record) {
 
 static bool json_is_timestamp(const DType& t) { return t.id >= QHIP_TIMESTAMP_S && t.id <= QHIP_TIMESTAMP_NS; }
 
-static bool json_decodable(const DType& t) {
+static bool json_decodable(const DType& t, int float_parse) {
+  if (float_parse >= 2 && t.id == QHIP_FLOAT32) return true;
   if (dtype_is_integer(t) || t.id == QHIP_BOOL || json_is_timestamp(t)) return true;   // (a zoned Timestamp never gets here: dtype_from_format refuses it)
   if (t.id == QHIP_DECIMAL128) return t.scale >= 0 && t.precision >= 1 && t.precision <= 38 && t.scale <= 38;
   return t.id == QHIP_FLOAT64 || t.id == QHIP_DATE32 || t.id == QHIP_UTF8;
@@ -53,7 +54,7 @@ qhip_table* table_from_json(Ctx* ctx, const ArrowSchema* schema, const uint8_t* 
   for (int64_t f = 0; f < nfields; ++f) {
     const ArrowSchema* cs = schema->children[f];
     const DType t = dtype_from_format(cs->format);   // (unknown formats, the null type among them: QHIP_UNSUPPORTED)
-    if (!json_decodable(t)) fail(QHIP_UNSUPPORTED, "JSON needs the host path: column type " + dtype_name(t) + " is not decoded on the device");
+    if (!json_decodable(t, ctx->float_parse)) fail(QHIP_UNSUPPORTED, "JSON needs the host path: column type " + dtype_name(t) + " is not decoded on the device");
     // (the host refuses a record in which a required field is absent or null; here a missing key and null are simply NULL)
     if (!(cs->flags & ARROW_FLAG_NULLABLE)) fail(QHIP_UNSUPPORTED, std::string("JSON needs the host path: schema field '") + (cs->name ? cs->name : "") + "' is not nullable");
     ftypes.push_back(t);
@@ -72,7 +73,8 @@ qhip_table* table_from_json(Ctx* ctx, const ArrowSchema* schema, const uint8_t* 
     else if (t.id == QHIP_BOOL) d.kind = QH_CSV_K_BOOL;
     else if (dtype_is_integer(t)) { d.kind = QH_CSV_K_INT; d.a = dtype_is_signed(t) ? 1 : 0; d.b = (uint8_t)dtype_width(t); }
     else if (t.id == QHIP_DATE32) d.kind = QH_CSV_K_DATE32;
-    else if (t.id == QHIP_FLOAT64) d.kind = QH_CSV_K_FLOAT64;
+    else if (t.id == QHIP_FLOAT64) d.kind = ctx->float_parse >= 2 ? QH_CSV_K_FLOAT64_FULL : QH_CSV_K_FLOAT64;   // (qhip_ctx_set_float_parse)
+    else if (t.id == QHIP_FLOAT32) d.kind = QH_CSV_K_FLOAT32;
     else if (json_is_timestamp(t)) { d.kind = QH_CSV_K_TIMESTAMP; d.a = (uint8_t)(3 * (t.id - QHIP_TIMESTAMP_S)); }
     else { d.kind = QH_CSV_K_DECIMAL128; d.a = (uint8_t)t.precision; d.b = (uint8_t)t.scale; }
   }

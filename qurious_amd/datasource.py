@@ -128,7 +128,10 @@ def read_csv(path: str, options: Optional[CsvReadOptions] = None, schema: Option
     (qhip_table_from_csv) and the result's `decoded_on_device` is True; a file outside the device's strict
     grammar falls back silently to the host parse below, which also produces every error message. What that grammar holds is
     the context's level (`Context.set_csv_grammar` / QHIP_CSV_GRAMMAR): 1, the default, plain fields only; 2 also quoted fields,
-    Boolean and Timestamp columns — with `schema=None` the types Arrow infers pass through as they are."""
+    Boolean and Timestamp columns — with `schema=None` the types Arrow infers pass through as they are. Float columns have a
+    level of their own (`Context.set_float_parse` / QHIP_FLOAT_PARSE): 1, the default, decodes a Float64 value only in Clinger's
+    exact range, so a file with one 17-digit `repr` value takes the host parse, and so does a Float32 column; 2 converts every
+    spelling -?[0-9]+(.[0-9]+)?([eE][-+]?[0-9]+)? on the device, correctly rounded, and admits Float32 columns."""
     import os
     o = options or CsvReadOptions()
     if device is None:
@@ -255,7 +258,9 @@ def read_json(path: str, batch_rows: Optional[int] = 1 << 20, schema: Optional[p
     (qhip_table_from_json) and the result's `decoded_on_device` is True. With `schema=None` the device takes the
     types Arrow infers from the file's first block. A file outside the device's strict grammar — nested values, \\uXXXX escapes,
     unknown or repeated keys, lenient number spellings, ... — falls back silently to the host read below, which also produces
-    every error message."""
+    every error message. Float64 numbers decode in Clinger's exact range only, and a Float32 field in the schema takes the host
+    read, unless the context's float_parse level (`Context.set_float_parse` / QHIP_FLOAT_PARSE) is 2: then every JSON number is
+    converted on the device, correctly rounded, to Float64 or Float32."""
     import os
     if device is None:
         device = os.environ.get("QHIP_JSON_DEVICE", "0") not in ("", "0")

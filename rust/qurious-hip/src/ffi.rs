@@ -196,6 +196,7 @@ extern "C" {
     pub fn qhip_ctx_set_wide_join_keys(ctx: *mut qhip_ctx, mode: i32) -> c_int;
     pub fn qhip_ctx_wide_key_joins(ctx: *mut qhip_ctx) -> i64;
     pub fn qhip_ctx_set_csv_grammar(ctx: *mut qhip_ctx, level: i32) -> c_int;
+    pub fn qhip_ctx_set_float_parse(ctx: *mut qhip_ctx, level: i32) -> c_int;
     pub fn qhip_ctx_allow_deferred_sizes(ctx: *mut qhip_ctx, delta: i32) -> c_int;
     pub fn qhip_ctx_forget_plans(ctx: *mut qhip_ctx) -> c_int;
 

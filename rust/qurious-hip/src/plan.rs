@@ -77,6 +77,9 @@ impl HipContext {
         // CSV text decoded on the device as ordinary writers produce it: quoted fields, and the Boolean and Timestamp columns
         // that arrow-rs' schema inference yields (datasource/file/csv.rs:56)
         unsafe { qhip_ctx_set_csv_grammar(raw, 2) };
+        // CSV and JSON text with real-valued columns as writers produce them too: shortest round-trip spellings of up to 17
+        // digits, exponents, Float32 columns, all converted on the device (correctly rounded or left to the host, never approximated)
+        unsafe { qhip_ctx_set_float_parse(raw, 2) };
         // Parquet files as writers produce them by default: Snappy pages are unpacked on the device instead of sending the
         // whole file to the host reader (datasource/file/parquet.rs)
         unsafe { qhip_ctx_set_parquet_format(raw, 2) };

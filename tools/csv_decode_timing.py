@@ -16,7 +16,14 @@ calls after --warmup calls, each ending in a device synchronise:
 whose values hold commas and, in a few percent of the rows, a doubled quote; the context decodes at grammar level 2
 (qhip_ctx_set_csv_grammar), without which such a file takes the host path.
 
+--floats repr: two more columns, Float64, written as the shortest round-trip text of random doubles (17 digits, what `repr` and
+every writer emit); the context decodes at float_parse level 2 (qhip_ctx_set_float_parse), without which the file's first such
+value sends it to the host. --floats round6: the same values rounded to 6 decimals, which level 1 decodes too; (a) .. (c) run at
+--float-parse (default 1) and (d) is taken at level 1, 2, 1, 2 on the one file: what the level-2 kinds cost a file that did
+not need them.
+
     python tools/csv_decode_timing.py [--gb 1.0] [--runs 10] [--warmup 2] [--repeat 2] [--threads 16] [--quoted]
+                                      [--floats repr|round6] [--float-parse 1|2]
 """
 import argparse
 import ctypes as C
@@ -56,12 +63,30 @@ def comment_column(first_row, n):
     return pa.array(pool, pa.string()).take(pa.array(idx))
 
 
-def write_file(path, target_bytes, quoted=False):
+FLOAT_NAMES = ["f_reading", "f_ratio"]
+
+
+def float_columns(first_row, n, mode):
+    """two Float64 columns of measurement-like values over ten decades, both signs. mode "repr": random doubles, which Arrow's
+    writer spells with their shortest round-trip digits (17, or 16 about as often); "round6": the same values rounded to 6
+    decimals, at most 13 digits: Clinger's range, what float_parse level 1 decodes"""
+    rng = np.random.default_rng(first_row + 1)
+    cols = []
+    for _ in FLOAT_NAMES:
+        v = rng.standard_normal(n) * np.power(10.0, rng.integers(-3, 7, n))
+        cols.append(pa.array(np.round(v, 6) if mode == "round6" else v))
+    return cols
+
+
+def write_file(path, target_bytes, quoted=False, floats=None):
     """lineitem rows until the file has about target_bytes; returns the row count"""
     step, rows = 1 << 20, 0
     with open(path, "wb") as f:
         while f.tell() < target_bytes:
             tbl = pa.Table.from_batches([synth.lineitem_batch(rows, step)])
+            if floats:
+                for name, col in zip(FLOAT_NAMES, float_columns(rows, step, floats)):
+                    tbl = tbl.append_column(name, col)
             if quoted:
                 tbl = tbl.append_column("l_comment", comment_column(rows, step))
             opts = pacsv.WriteOptions(include_header=rows == 0) if quoted else pacsv.WriteOptions(include_header=rows == 0, quoting_style="none")
@@ -89,10 +114,17 @@ def main():
     ap.add_argument("--repeat", type=int, default=2)
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--quoted", action="store_true", help="Arrow's default quoting and a comment column with commas and doubled quotes; grammar level 2")
+    ap.add_argument("--floats", choices=["repr", "round6"], help="two Float64 columns: shortest round-trip spellings of random doubles / the same rounded to 6 decimals")
+    ap.add_argument("--float-parse", type=int, choices=[1, 2], help="the context's float_parse level (default: 2 with --floats repr, else 1)")
     args = ap.parse_args()
     pa.set_cpu_count(args.threads)
     ctx = q.get_context()
     schema = pa.schema([pa.field(f.name, f.type) for f in synth.LINEITEM_SCHEMA])
+    float_parse = args.float_parse or (2 if args.floats == "repr" else 1)
+    ctx.set_float_parse(float_parse)
+    if args.floats:
+        for name in FLOAT_NAMES:
+            schema = schema.append(pa.field(name, pa.float64()))
     if args.quoted:
         schema = schema.append(pa.field("l_comment", pa.string()))
         ctx.set_csv_grammar(2)
@@ -100,9 +132,11 @@ def main():
     hip.hipMalloc.argtypes, hip.hipMemcpy.argtypes, hip.hipFree.argtypes = [C.POINTER(C.c_void_p), C.c_size_t], [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int], [C.c_void_p]
     with tempfile.TemporaryDirectory() as d:
         path = os.path.join(d, "lineitem.csv")
-        rows = write_file(path, int(args.gb * 1e9), args.quoted)
+        rows = write_file(path, int(args.gb * 1e9), args.quoted, args.floats)
         nbytes = os.path.getsize(path)
         kind = ", default quoting, grammar 2" if args.quoted else ""
+        if args.floats:
+            kind += f", two Float64 columns ({args.floats}), float_parse {float_parse}"
         print(f"device {ctx.device_name()}; {path}: {nbytes} bytes, {rows} rows, {nbytes / rows:.1f} bytes per record{kind}; median (min) of {args.runs} calls "
               f"after {args.warmup} warm-up calls; host parse with {args.threads} threads", flush=True)
 
@@ -133,18 +167,24 @@ def main():
                 med, low = median_ms(fn, args.runs, args.warmup)
                 print(f"run {rep + 1} {name:30s} {med:9.2f} ms (min {low:9.2f})  {nbytes / med / 1e6:8.2f} GB/s of file bytes", flush=True)
         ctx.set_timing(True)
-        per = []
-        for _ in range(args.warmup + args.runs):
-            device_path()
-            per.append(ctx.csv_pass_ms())
+        # (a round6 file is inside both levels' grammar: the passes at either level, alternating, are what the level-2 kinds cost
+        # a file that did not need them)
+        levels = [1, 2, 1, 2] if args.floats == "round6" else [float_parse]
+        for level in levels:
+            ctx.set_float_parse(level)
+            per = []
+            for _ in range(args.warmup + args.runs):
+                device_path()
+                per.append(ctx.csv_pass_ms())
+            per = per[args.warmup:]
+            kernels = 0.0
+            tag = f"(d) float_parse {level} " if args.floats else "(d) "
+            for k, name in enumerate(PASSES):
+                med = statistics.median(p[k] for p in per)
+                kernels += med if k else 0.0
+                print(f"{tag}{name:32s} {med:9.3f} ms  {nbytes / max(med, 1e-6) / 1e6:9.1f} GB/s of file bytes", flush=True)
+            print(f"{tag}kernels together (all but the upload) {kernels:9.3f} ms  {nbytes / max(kernels, 1e-6) / 1e6:9.1f} GB/s of file bytes", flush=True)
         ctx.set_timing(False)
-        per = per[args.warmup:]
-        kernels = 0.0
-        for k, name in enumerate(PASSES):
-            med = statistics.median(p[k] for p in per)
-            kernels += med if k else 0.0
-            print(f"(d) {name:32s} {med:9.3f} ms  {nbytes / max(med, 1e-6) / 1e6:9.1f} GB/s of file bytes", flush=True)
-        print(f"(d) kernels together (all but the upload) {kernels:9.3f} ms  {nbytes / max(kernels, 1e-6) / 1e6:9.1f} GB/s of file bytes", flush=True)
         del src
         m.close()
         f.close()
